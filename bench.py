@@ -1,7 +1,7 @@
 """Throughput benchmark: DenseCLIP ViT-B/16 fwd+bwd training step at 1024x2048 (BASELINE.json
 metric, configs[1] per GPU: batch 8 per GPU, bf16), data-parallel over RCCL for N > 1.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode F|R]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode F|R] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 `--gpus N > 1` without a launcher: this process makes NO HIP call; it starts
@@ -17,6 +17,12 @@ gradient all-reduce (DDP over RCCL when N > 1) and AdamW.  Mode F (default, full
 fine-tune) trains the ViT too, so its backward kernels run; mode R is the reference
 trainer's regime (backbone + text encoder frozen, train_denseclip.py:1040-1044) and is
 measured as well and reported beside the headline.
+
+A plain run sets up, warms up, times the K steps (`ms_per_step` = the milliseconds one timed step
+took), writes the last timed step's outputs under `--dump-outputs DIR` and prints the line.  Every
+other measurement (the per-op breakdown pass, mode R, fp16, the fp8 / ViT-L/14 / inference / ddp1
+configurations, the CPU baselines) runs only with `--full`, each still switched off by its `--no-*`
+option.
 
 rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel of a train step (the
 attention backward: dQ + dK/dV passes; `roofline_attn_fwd` for the forward), timed with HIP
@@ -95,6 +101,14 @@ def parse(argv=None):
                          "and the configs[0] CPU forward")
     ap.add_argument("--no-op-timing", action="store_true",
                     help="no per-op HIP-event breakdown (`ops` objects) of the headline and fp16 steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other measurement (per-op breakdown pass, mode R, fp16, "
+                         "fp8 / ViT-L/14 / inference / ddp1 configurations, CPU baselines); without it the run "
+                         "only times the headline steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned and left behind as DIR/<name>.npy (float32): "
+                         "training: loss, and a fixed seeded sample of every trainable parameter's gradient and "
+                         "updated value; --infer: a fixed seeded sample of seg and depth")
     return ap.parse_args(argv)
 
 
@@ -179,7 +193,9 @@ def make_model(dev, mode, arch="vitb16"):
     return model
 
 
-def run_steps(model, opt, batch, steps, silog):
+def run_steps(model, opt, batch, steps, silog, keep=None):
+    """`keep` (a dict) receives what the last step returned: "loss" of a train step, the "out" dict of
+    an inference forward (--dump-outputs)."""
     from denseclip_vit_multimodal_amd.train import train_step
     loss = None
     for _ in range(steps):
@@ -187,14 +203,62 @@ def run_steps(model, opt, batch, steps, silog):
             with torch.no_grad():
                 out = model(batch[0], return_loss=False)
             loss = out["seg"][0, 0, 0, 0]
+            if keep is not None:
+                keep["out"] = out
         else:
             loss = train_step(model, opt, batch, silog)
+            if keep is not None:
+                keep["loss"] = loss
     return loss
 
 
-def timed(model, opt, batch, steps, warmup, silog, world, dist_on=None, op_timing=False):
+DUMP_PER_TENSOR = 4096  # sampled elements per parameter (ViT-B/16 mode F: 424468 floats, 1.7 MB per file)
+DUMP_PER_OUTPUT = 1 << 20  # sampled elements per inference output (4 MB per file)
+
+
+def _sample(t, n, gen):
+    """A fixed sample of t's elements as float32 on the host: all of them when t has at most n, else
+    n flat indices drawn from the seeded CPU generator (the same indices for the same shapes)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        flat = flat[torch.randint(0, flat.numel(), (n,), generator=gen).to(flat.device)]
+    return flat.float().cpu()
+
+
+def dump_outputs(path, model, kept):
+    """--dump-outputs: the last timed step's results as float32 .npy files.  A train step returns
+    its loss and leaves the gradients and the AdamW-updated parameters behind (loss.npy, grads.npy,
+    params.npy: per trainable parameter in named_parameters() order a seeded sample of
+    DUMP_PER_TENSOR elements, concatenated; a parameter without a gradient contributes zeros); an
+    inference forward returns seg and depth (seg.npy, depth.npy: seeded samples)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    gen = torch.Generator(device="cpu").manual_seed(4321)
+    arrays = {}
+    if "out" in kept:
+        for name in ("seg", "depth"):
+            if kept["out"].get(name) is not None:
+                arrays[name] = _sample(kept["out"][name], DUMP_PER_OUTPUT, gen)
+    else:
+        arrays["loss"] = kept["loss"].detach().float().reshape(1).cpu()
+        grads, params = [], []
+        for _, p in getattr(model, "module", model).named_parameters():
+            if not p.requires_grad:
+                continue
+            state = gen.get_state()
+            params.append(_sample(p, DUMP_PER_TENSOR, gen))
+            gen.set_state(state)  # the gradient at the same indices as the value
+            grads.append(_sample(p.grad if p.grad is not None else torch.zeros_like(p), DUMP_PER_TENSOR, gen))
+        arrays["grads"] = torch.cat(grads)
+        arrays["params"] = torch.cat(params)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.numpy().astype(np.float32))
+
+
+def timed(model, opt, batch, steps, warmup, silog, world, dist_on=None, op_timing=False, keep=None):
     """(seconds for `steps` steps, max over ranks; per-op HIP-event summary; last loss).
-    op_timing also brackets every torch.ops.dclip launch with events (ops.TIMING_OPS)."""
+    op_timing also brackets every torch.ops.dclip launch with events (ops.TIMING_OPS); `keep` as
+    run_steps."""
     from denseclip_vit_multimodal_amd import ops
     dist_on = world > 1 if dist_on is None else dist_on
     run_steps(model, opt, batch, warmup, silog)
@@ -204,7 +268,7 @@ def timed(model, opt, batch, steps, warmup, silog, world, dist_on=None, op_timin
     ops.TIMING = {}
     ops.TIMING_OPS = bool(op_timing)
     t0 = time.perf_counter()
-    loss = run_steps(model, opt, batch, steps, silog)
+    loss = run_steps(model, opt, batch, steps, silog, keep)
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
@@ -304,7 +368,9 @@ def main():
     if spawn:  # N ranks as a child process; this parent makes no HIP call at all
         sys.exit(spawn_ranks(sys.argv[1:], world))
     FUSED_HEAD_LOSS = not args.unfused_head_loss
-    rank = int(os.environ.get("RANK", "0"))
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("bench.py: --dump-outputs writes the last timed step's outputs; --steps must be >= 1")
+    rank =int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dist_on = world > 1 or args.ddp
     rccl_ranks = None
@@ -347,7 +413,7 @@ def main():
         bb = ARCHS[arch] or dict(patch_size=16, heads=12)
         return (H // bb["patch_size"]) * (W // bb["patch_size"]) + 1, bb["heads"]
 
-    op_timing = not args.no_op_timing
+    op_timing = args.full and not args.no_op_timing
 
     def op_pass(model, opt, batch_, steps=2):
         """The per-op breakdown from its OWN short pass after the timed region: HIP events around
@@ -358,7 +424,11 @@ def main():
         return op_breakdown(so, steps, dto / steps * 1e3)
 
     model, opt = setup(args.mode)
-    dt, summ, loss = timed(model, opt, batch, args.steps, args.warmup, silog, world, dist_on)
+    kept = {} if args.dump_outputs and rank == 0 else None
+    dt, summ, loss = timed(model, opt, batch, args.steps, args.warmup, silog, world, dist_on, keep=kept)
+    if kept is not None:
+        dump_outputs(args.dump_outputs, model, kept)
+        kept = None
     ops_head = op_pass(model, opt, batch)
     value = world * B * args.steps / dt
     progress(f"headline {dt / args.steps * 1e3:.2f} ms per step")
@@ -403,7 +473,7 @@ def main():
 
     k_sub = max(3, args.steps // 2)
     mode_r = None
-    if args.mode == "F" and not args.no_mode_r and not args.infer:
+    if args.full and args.mode == "F" and not args.no_mode_r and not args.infer:
         release()
         model, opt = setup("R")
         dtr, _, _ = timed(model, opt, batch, k_sub, 2, silog, world, dist_on)
@@ -413,7 +483,8 @@ def main():
                   "what": "reference regime: backbone + text encoder frozen (train_denseclip.py:1040-1044)"}
 
     fp16 = None
-    if args.mode == "F" and not args.no_fp16 and not args.infer and args.dtype == "bf16" and not args.attn_fp8:
+    if args.full and args.mode == "F" and not args.no_fp16 and not args.infer and args.dtype == "bf16" \
+            and not args.attn_fp8:
         # the 1e-3 dtype: fp32 images (what the reference trainer feeds), fp16 compute
         release()
         model, opt = setup("F", torch.float16)
@@ -434,7 +505,7 @@ def main():
                             for k, v in s16.items() if not k.startswith("op:")},
                 "ops": ops16}
 
-    extras = not args.no_extras and args.mode == "F" and not args.infer and args.arch == "vitb16" \
+    extras = args.full and not args.no_extras and args.mode == "F" and not args.infer and args.arch == "vitb16" \
         and not args.attn_fp8 and args.dtype == "bf16" and (H, W) == (1024, 2048)
     fp8 = None
     vitl14 = None
@@ -582,7 +653,8 @@ def main():
     release()
 
     cpu = cpu0 = None
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto" and args.arch == "vitb16" and not args.infer:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline == "auto" and args.arch == "vitb16" \
+            and not args.infer:
         threads = args.cpu_threads or min(16, os.cpu_count() or 1)
         try:
             progress("cpu baseline")
@@ -631,6 +703,7 @@ def main():
             "rccl_ranks": rccl_ranks,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(dt / args.steps * 1e3, 2),
             "higher_is_better": True,
             "scaling": "weak",

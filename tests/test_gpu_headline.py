@@ -170,6 +170,25 @@ def test_bench_rccl_ddp_world_size_1(grad_dtype):
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["loss"] == line["loss"]  # finite, not NaN
 
 
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, runs none of the extra measurements and
+    writes the last timed step's loss, gradient and parameter samples as float32 .npy files; mode F
+    at 128x256."""
+    import numpy as np
+    line = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--height", "128", "--width",
+                   "256", "--dump-outputs", str(tmp_path)], port=29575)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 1.0) < 1e-2  # batch 1
+    for k in ("ops", "mode_R", "fp16", "fp8", "vitl14", "infer", "ddp1", "cpu_baseline", "cpu_baseline_cfg0"):
+        assert line[k] is None, k
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in ("loss", "grads", "params")}
+    assert sorted(os.listdir(tmp_path)) == ["grads.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert round(float(got["loss"][0]), 4) == line["loss"]
+    assert got["grads"].shape == got["params"].shape and got["grads"].size > 100 * 4096 and got["grads"].any()
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) < 64 * 2 ** 20
+
+
 def test_grad_allreduce_rccl_world_size_1():
     """train.GradAllReduce's RCCL path (coalesced and per-tensor in-place AVG all-reduces launched
     from the backward's post-accumulate-grad hooks, ~1 MB buckets) on a one-rank "nccl" group with
