@@ -2463,7 +2463,9 @@ bool bwd2_launch(const void* qkv, const void* o, const void* dout, const float* 
     if (N < 257 || dclip_option(DCLIP_OPT_ATTN_BWD_KERNEL) == 1) return false;
     // a ragged N - 1 (partial last query / key blocks, masked tails) in the default passes only
     const bool ragged = (N - 1) % 256 != 0;
-    const int bwd_block = dclip_option(DCLIP_OPT_ATTN_BWD_BLOCK);
+    // the fp8 backward has one CLS-split form (dq2 + dkdv8 + the fold merge, what option 0 selects):
+    // DCLIP_OPT_ATTN_BWD_BLOCK picks among the 16-bit dK/dV passes only and is not read for it
+    const int bwd_block = f8ws != nullptr ? 0 : dclip_option(DCLIP_OPT_ATTN_BWD_BLOCK);
     if (ragged && (dclip_option(DCLIP_OPT_ATTN_DQ_WAVES) == 4 ||
                    (bwd_block != 0 && bwd_block != 5 && bwd_block != 6 && bwd_block != 7 && bwd_block != 8 &&
                     bwd_block != 9 && bwd_block != 10)))
@@ -2620,13 +2622,21 @@ static int64_t bwd_ws_two_pass(int B, int N, int H) {
     return 3 * (int64_t)B * H * N + (int64_t)B * H * ((N + 63) / 64) * 192;
 }
 
+// Independent of every option (a size queried under one option serves a launch under any other):
+// for N >= 257 the one-pass backward's (the largest form: + dS_q0 (B*H*N) + the dQ partials), below
+// it the two-pass part alone
 extern "C" int64_t dclip_attn_bwd_workspace(int B, int N, int H) {
     const int64_t two_pass = bwd_ws_two_pass(B, N, H);
-    // the one-pass backward (the default, options 9 / 10): + dS_q0 (B*H*N) + the dQ partials
-    const int blk = dclip_option(DCLIP_OPT_ATTN_BWD_BLOCK);
-    if ((blk == 0 || blk == 9 || blk == 10) && N >= 257 && dclip_option(DCLIP_OPT_ATTN_BWD_KERNEL) != 1)
-        return two_pass + (int64_t)B * H * N + (attn_bwd1_part_bytes(B, N, H) + 3) / 4 + 64;
+    if (N >= 257) return two_pass + (int64_t)B * H * N + (attn_bwd1_part_bytes(B, N, H) + 3) / 4 + 64;
     return two_pass;
+}
+
+// whether dclip_attn_bwd takes the one-pass branch of bwd2_launch (same conditions, same order)
+static bool bwd_one_pass(int N) {
+    if (N < 257 || dclip_option(DCLIP_OPT_ATTN_BWD_KERNEL) == 1) return false;
+    if ((N - 1) % 256 != 0 && dclip_option(DCLIP_OPT_ATTN_DQ_WAVES) == 4) return false;
+    const int blk = dclip_option(DCLIP_OPT_ATTN_BWD_BLOCK);
+    return blk == 0 || blk == 9 || blk == 10;
 }
 
 extern "C" int dclip_attn_bwd(int dt, const void* qkv, const void* o, const void* dout, const float* lse,
@@ -2634,6 +2644,12 @@ extern "C" int dclip_attn_bwd(int dt, const void* qkv, const void* o, const void
     DCLIP_HOST_CHECK(D == HD, "dclip_attn_bwd: head_dim must be 64 (got %d)", D);
     DCLIP_HOST_CHECK(dt == DCLIP_BF16 || dt == DCLIP_F16, "dclip_attn_bwd: dtype must be f16/bf16");
     DCLIP_HOST_CHECK(B > 0 && N > 0 && H > 0, "dclip_attn_bwd: empty problem");
+    // the one-pass sweep addresses an (image, head)'s dQ partials through a buffer resource with 32-bit
+    // num_records and store offsets: (1 + 64 ceil((N-1)/64)) rows of ceil((N-1)/256) * 128 bytes
+    DCLIP_HOST_CHECK(!bwd_one_pass(N) ||
+                         (1 + 64 * (int64_t)((N - 1 + 63) / 64)) * (int64_t)((N - 1 + 255) / 256) * 128 < (1ll << 32),
+                     "dclip_attn_bwd: N too large for the one-pass backward's dQ partials (N = %d; "
+                     "DCLIP_OPT_ATTN_BWD_BLOCK 6 selects the two-pass backward)", N);
     hipStream_t st = (hipStream_t)stream;
     if (dt == DCLIP_BF16) bwd_launch<bf16>(qkv, o, dout, lse, delta_ws, dqkv, B, N, H, scale, st);
     else bwd_launch<f16>(qkv, o, dout, lse, delta_ws, dqkv, B, N, H, scale, st);
@@ -2641,7 +2657,10 @@ extern "C" int dclip_attn_bwd(int dt, const void* qkv, const void* o, const void
     return 0;
 }
 
-// configs[4]'s backward (include/dclip.h): dclip_attn_bwd's workspace, then the fp8 images
+// configs[4]'s backward (include/dclip.h): dclip_attn_bwd's two-pass workspace, then the fp8 images.
+// Its CLS-split path (N >= 257, not DCLIP_OPT_ATTN_BWD_KERNEL 1, not a ragged N - 1 with
+// DCLIP_OPT_ATTN_DQ_WAVES 4) is dq2 + dkdv8 + the fold merge under every DCLIP_OPT_ATTN_BWD_BLOCK
+// value; everything else runs dclip_attn_bwd's generic 16-bit passes
 extern "C" int64_t dclip_attn_bwd_fp8_workspace(int B, int N, int H) {
     return bwd_ws_two_pass(B, N, H) + (attn_bwd_fp8_ws_bytes(B, N, H) + 3) / 4 + 64;
 }

@@ -179,11 +179,16 @@ int dclip_attn_fwd(int dt, const void* qkv, void* o, float* lse,
  * rowsum(dout*o) and the statistics, one key-major sweep for dK, dV and 16-bit dQ partials per
  * 256-key block, an ordered reduction of the partials); with DCLIP_OPT_ATTN_BWD_BLOCK 6, and below
  * N = 257, a query-major dQ pass (which also writes delta) and a key-major dK/dV pass.  dout:
- * (B*N, H*D) dt.  delta_ws: f32 workspace of dclip_attn_bwd_workspace(B, N, H) floats — query it
- * after setting options: it includes the one-pass form's partials (B*H*ceil((N-1)/256)*
- * (1+64*ceil((N-1)/64))*128 bytes, 3.2 GB at B = 8, N = 8193, H = 12) when that form runs.  Its
+ * (B*N, H*D) dt.  delta_ws: f32 workspace of dclip_attn_bwd_workspace(B, N, H) floats, a function
+ * of (B, N, H) alone — no option changes it, so a size queried once serves a launch under any
+ * option: for N >= 257 it includes the one-pass form's partials (B*H*ceil((N-1)/256)*
+ * (1+64*ceil((N-1)/64))*128 bytes, 3.2 GB at B = 8, N = 8193, H = 12), the largest form; below 257
+ * it is the two-pass part alone.  Its contents on entry are irrelevant.  Its
  * first B*H*N floats receive delta; the rest holds the CLS-split row-0 partials, the negated lse /
- * delta planes, key 0's dS column and the dQ partials.
+ * delta planes, key 0's dS column and the dQ partials.  The one-pass form addresses an (image,
+ * head)'s partials with 32-bit offsets: when (1+64*ceil((N-1)/64))*ceil((N-1)/256)*128 >= 2^32
+ * (N above about 92.7k) the call fails with DCLIP_ERR_ARG ("N too large") before any launch;
+ * DCLIP_OPT_ATTN_BWD_BLOCK 6 (the two-pass backward) has no such limit.
  * qkv as for dclip_attn_fwd (q pre-multiplied by scale*log2(e)); `scale` = d^-0.5.
  * dqkv: (B*N, 3*H*D) dt output, [dq | dk | dv] in the qkv layout: gradients with
  * respect to the UNSCALED q, k, v (i.e. the in-projection output before the q scale).  */
@@ -195,8 +200,14 @@ int dclip_attn_bwd(int dt, const void* qkv, const void* o, const void* dout,
  * rounding — on the CLS-split path (N >= 257) the dK / dV pass runs dV = P^T dO and dK = dS^T q' on
  * the block-scaled e4m3 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, MX E8M0 scales per 32 queries: the
  * Q / dO rows' from a pack pass, P's fixed at 2^-8, dS's per key from its amax), S, dP and the dQ
- * pass stay 16-bit; elsewhere it is dclip_attn_bwd.  ws: dclip_attn_bwd_fp8_workspace(B, N, H)
- * floats, 16-B aligned (dclip_attn_bwd's workspace, then the slices' e4m3 images).  Replaces the
+ * pass stay 16-bit; elsewhere it is dclip_attn_bwd.  The CLS-split path has this one form (the dQ
+ * pass, the e4m3 dK / dV pass, the fold merge): DCLIP_OPT_ATTN_BWD_BLOCK selects among the 16-bit
+ * dK / dV passes and is NOT read here — every value gives the result of 0, a ragged N - 1
+ * included (the DCLIP_OPT_ATTN_DQ_* options still pick the dQ pass's variant).  "Elsewhere" is
+ * N < 257, DCLIP_OPT_ATTN_BWD_KERNEL 1, and a ragged N - 1 (not a multiple of 256) with
+ * DCLIP_OPT_ATTN_DQ_WAVES 4: those run dclip_attn_bwd's generic 16-bit passes, bit for bit its
+ * result under the same options.  ws: dclip_attn_bwd_fp8_workspace(B, N, H)
+ * floats, 16-B aligned (dclip_attn_bwd's two-pass workspace, then the slices' e4m3 images).  Replaces the
  * backward of models.py:287-289 under the fp8 attention of BASELINE configs[4].               */
 int64_t dclip_attn_bwd_fp8_workspace(int B, int N, int H);
 int dclip_attn_bwd_fp8(int dt, const void* qkv, const void* o, const void* dout, const float* lse, float* ws,

@@ -1,0 +1,121 @@
+"""Guard-banded, poisoned buffers for tests that call the C ABI directly (test_gpu_abi_contract.py).
+
+The op layer allocates every output and workspace with at::empty, and the caching allocator hands a
+second call the block the first one just freed — still holding the first call's (correct) result.
+A row a kernel never writes, or a workspace partial it reads before writing, then looks right.
+Here every buffer is a slice of one flat uint8 allocation
+
+    [ 1 MiB guard | payload | 1 MiB guard ]
+
+with both guards filled with 0xFF (NaN as f32, f16 and bf16) and the payload with a byte of the
+caller's choice, so that
+  * an input is followed (and preceded) by NaN: a tile that reads past the last row and multiplies
+    what it read by zero gives NaN instead of 0;
+  * an out-of-bounds write of up to 1 MiB lands in a guard, harmlessly, and is seen by check();
+  * run_poisoned() runs an entry point on outputs / workspaces pre-filled with 0xFF and again with
+    0x3C (finite in every dtype): NaN after the first run means something was read before it was
+    written, a difference between the runs means an output depends on what the buffers held.
+Workspaces are sized by the library's own queries, never smaller.
+"""
+import contextlib
+
+import torch
+
+DEV = "cuda"
+GUARD = 1 << 20
+POISON, FINITE = 0xFF, 0x3C
+
+
+class Guarded:
+    """A typed tensor `t` of `shape` inside [1 MiB 0xFF | payload | 1 MiB 0xFF]: the payload starts
+    256-B aligned and the trailing guard at the first byte after its last element."""
+
+    def __init__(self, shape, dtype, fill=0):
+        shape = (int(shape),) if isinstance(shape, int) else tuple(int(s) for s in shape)
+        n = 1
+        for s in shape:
+            n *= s
+        self.nbytes = n * torch.empty((), dtype=dtype).element_size()
+        self.raw = torch.empty(GUARD + 256 + self.nbytes + GUARD, dtype=torch.uint8, device=DEV)
+        self.off = GUARD + (-(self.raw.data_ptr() + GUARD)) % 256
+        self.raw.fill_(POISON)
+        self.t = self.raw[self.off:self.off + self.nbytes].view(dtype).view(shape)
+        assert self.t.data_ptr() % 256 == 0 and self.t.data_ptr() == self.raw.data_ptr() + self.off
+        self.fill(fill)
+
+    def fill(self, byte):
+        self.raw[self.off:self.off + self.nbytes] = byte
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def intact(self):
+        """0-d bool tensor (no synchronisation): both guards still all 0xFF"""
+        return (self.raw[:self.off] == POISON).all() & (self.raw[self.off + self.nbytes:] == POISON).all()
+
+    def check(self):
+        assert bool(self.intact()), "a guard band was written: out-of-bounds write"
+
+
+def guarded(nbytes_or_shape, dtype=torch.uint8, fill=0):
+    return Guarded(nbytes_or_shape, dtype, fill)
+
+
+def guarded_copy(t):
+    """`t`'s values in a guarded buffer: NaN follows the last element"""
+    g = Guarded(t.shape, t.dtype)
+    g.t.copy_(t)
+    return g
+
+
+def bits(t):
+    """integer view for bitwise comparisons (NaN == NaN, -0 != +0)"""
+    return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def bitwise_equal(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
+
+
+def run_poisoned(fn, inputs=(), outputs=(), scratch=(), accum=()):
+    """Call `fn()` (one entry point through _native.call, on the current stream) twice on the same
+    inputs: with `outputs` and `scratch` (Guarded) filled with 0xFF, then with 0x3C; `accum`
+    (accumulating arguments the caller initialises by contract) zeroed before each.  Then, in this
+    order: every guard of every buffer intact, the 0xFF run's outputs all finite, the two runs'
+    outputs bitwise equal.  Returns the outputs' (then the accumulators') values."""
+    runs = []
+    for byte in (POISON, FINITE):
+        for g in tuple(outputs) + tuple(scratch):
+            g.fill(byte)
+        for g in accum:
+            g.fill(0)
+        fn()
+        runs.append([g.t.clone() for g in tuple(outputs) + tuple(accum)])
+    ok = [g.intact() for g in tuple(inputs) + tuple(outputs) + tuple(scratch) + tuple(accum)]
+    torch.cuda.synchronize()
+    broken = [i for i, v in enumerate(ok) if not bool(v)]
+    assert not broken, f"out-of-bounds write: guard bands of buffers {broken} (inputs, outputs, scratch, accum) changed"
+    for i, t in enumerate(runs[0]):
+        assert bool(torch.isfinite(t).all()), \
+            f"output {i}: {int((~torch.isfinite(t)).sum())} non-finite values after the 0xFF run (read before written)"
+    for i, (a, b) in enumerate(zip(*runs)):
+        assert bitwise_equal(a, b), \
+            f"output {i} depends on the buffers' contents on entry ({int((bits(a) != bits(b)).sum())} elements differ)"
+    return runs[0]
+
+
+@contextlib.contextmanager
+def option_scope():
+    """yields set(option id, value); every option touched is back at 0 on exit"""
+    from denseclip_vit_multimodal_amd import _native as NT
+    touched = []
+
+    def set_option(opt, value):
+        touched.append(opt)
+        NT.call("dclip_set_option", opt, int(value))
+
+    try:
+        yield set_option
+    finally:
+        for opt in touched:
+            NT.call("dclip_set_option", opt, 0)

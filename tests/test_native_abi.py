@@ -50,12 +50,54 @@ def test_no_oracle_in_product_package():
     (lambda L: L.dclip_score_map(None, 2, 0, 0, 512, None, None, 1, 4, 512, 40, 1e-12, None), "K must be"),
     (lambda L: L.dclip_row_mean(None, 2, 0, 0, 100, 1, 4, 100, None, None, None), "C % 8"),
     (lambda L: L.dclip_im2col(None, 0, None, 0, 768, 1, 3, 8, 8, 16, None), "smaller than one patch"),
+    # the one-pass backward's dQ partials of one (image, head) past 32-bit offsets: rejected before any launch
+    (lambda L: L.dclip_attn_bwd(2, None, None, None, None, None, None, 1, 131073, 1, 64, 0.125, None), "N too large"),
 ])
 def test_argument_errors_are_reported(call, needle):
     L = N.load()
     rc = call(L)
     assert rc == -1
     assert needle in L.dclip_last_error().decode()
+
+
+@pytest.mark.parametrize("B,Ntok,H", [(8, 8193, 12), (2, 290, 3), (1, 65, 1)])
+def test_attn_bwd_workspace_ignores_options(B, Ntok, H):
+    """dclip_attn_bwd_workspace(B, N, H) is a function of its arguments alone: a caller that sizes
+    the workspace under one DCLIP_OPT_ATTN_BWD_BLOCK / _KERNEL setting and launches under another
+    (tools/ab_attn_opt.py does) never holds too small a buffer.  For N >= 257 it covers the largest
+    form: the two-pass part, key 0's dS column and the one-pass backward's dQ partials."""
+    L = N.load()
+    sizes = set()
+    try:
+        for kern in (0, 1):
+            assert L.dclip_set_option(N.OPT_ATTN_BWD_KERNEL, kern) == 0
+            for blk in range(11):
+                assert L.dclip_set_option(N.OPT_ATTN_BWD_BLOCK, blk) == 0
+                sizes.add(L.dclip_attn_bwd_workspace(B, Ntok, H))
+    finally:
+        L.dclip_set_option(N.OPT_ATTN_BWD_KERNEL, 0)
+        L.dclip_set_option(N.OPT_ATTN_BWD_BLOCK, 0)
+    assert len(sizes) == 1, sorted(sizes)
+    two_pass = 3 * B * H * Ntok + B * H * ((Ntok + 63) // 64) * 192
+    if Ntok >= 257:
+        part_bytes = B * H * ((Ntok - 1 + 255) // 256) * (1 + 64 * ((Ntok - 1 + 63) // 64)) * 128
+        assert min(sizes) >= two_pass + B * H * Ntok + part_bytes // 4
+    else:
+        assert sizes == {two_pass}
+
+
+def test_attn_bwd_too_long_names_the_way_out():
+    """the one-pass limit's message names the option that lifts it, and the first N at which the dQ
+    partials of one (image, head) reach 2^32 bytes is already rejected (both calls fail in the host
+    check, before any launch: the pointers are null)"""
+    L = N.load()
+    args = lambda n: (2, None, None, None, None, None, None, 1, n, 1, 64, 0.125, None)  # noqa: E731
+    assert L.dclip_attn_bwd(*args(131073)) == -1
+    assert "DCLIP_OPT_ATTN_BWD_BLOCK 6" in L.dclip_last_error().decode()
+    # (1 + 64 ceil((N-1)/64)) ceil((N-1)/256) 128 >= 2^32 first at N - 1 = 362 * 256 + 1
+    limit = next(n for n in range(90000, 95000)
+                 if (1 + 64 * ((n - 1 + 63) // 64)) * ((n - 1 + 255) // 256) * 128 >= 1 << 32)
+    assert L.dclip_attn_bwd(*args(limit)) == -1 and "N too large" in L.dclip_last_error().decode()
 
 
 def test_missing_library_fails_loudly(tmp_path):
