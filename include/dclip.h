@@ -4,8 +4,14 @@
  * Every entry point takes plain device pointers, element counts/strides and a
  * hipStream_t (passed as void*), launches asynchronously on that stream and returns
  * 0 on success or a negative DCLIP_ERR_* code; dclip_last_error() then holds a
- * message (thread-local).  No entry point allocates, synchronises or touches the
- * host side of a tensor, so a caller may capture any sequence in a hipGraph.
+ * message (thread-local).  No entry point synchronises or touches the host side of a
+ * tensor, and workspaces are the caller's.  Two entry points allocate device memory
+ * themselves, on first use per device: dclip_conv3x3* (one row of zeros, once) and
+ * dclip_gemm (the scratch of its M-tail split, regrown whenever a call needs more than
+ * any call before it, and shared by all calls: one stream at a time).  So run one
+ * warm-up call of every shape before capturing a sequence in a hipGraph; after that a
+ * caller may capture any sequence.  (DCLIP_OPT_GEMM_SCHED 1 also allocates its claim
+ * counters on first use.)
  *
  * dtype codes: DCLIP_F32 / DCLIP_F16 / DCLIP_BF16.  Matrices are row-major with
  * explicit leading dimensions (in elements).
@@ -137,7 +143,19 @@ int64_t dclip_layernorm_bwd_ws_floats(int64_t rows, int64_t cols);
  * alpha undoes a gradient scale carried by an operand (fp16 backward; 1 otherwise); when
  * alpha_ptr is non-null the factor is alpha * *alpha_ptr, read on the device (the 1/s entry
  * of a dclip_grad_scale pair: no host round trip).
- * splits > 1 (EPI_SPLITK only) splits K into `splits` equal 64-multiple chunks.      */
+ * splits > 1 (EPI_SPLITK only) splits K into `splits` equal 64-multiple chunks.
+ * Alignment, as the kernels access memory today: a run of 8 consecutive columns of a row
+ * of C, C2 or aux (RESIDUAL: f32, GELU_BWD: ab_dt) is one 16-byte access in a 16-bit matrix
+ * and two in an f32 one (the persistent kernel: 4 columns, 8 or 16 bytes), and bias and
+ * STORE_SCALED's scale vector are read 4 or 8 floats at a time.  Hence
+ *   A, B, C, C2, aux, bias: 16-byte aligned (A and B: checked);
+ *   lda, ldb % 8 == 0 (checked); ldc, ldc2, ld_aux % 8 == 0 for a 16-bit matrix, % 4 == 0
+ *   for an f32 one (checked for RESIDUAL's C and aux and for SPLITK's C only).
+ * N need not be a multiple of 8: a row's last, partial run is accessed element by element.
+ * What is not checked is not rejected: the persistent kernel declines a call whose bias /
+ * scale vector is not 16-byte aligned or whose ldc, ldc2 or ld_aux is not a multiple of 4
+ * (the grid kernel runs instead), and every other kernel then issues unaligned vector
+ * accesses, which no test covers.                                                      */
 int dclip_gemm(int epilogue, int ab_dt,
                const void* A, int64_t lda, const void* B, int64_t ldb,
                int64_t M, int64_t N, int64_t K, int splits, float alpha, const float* alpha_ptr,

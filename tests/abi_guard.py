@@ -1,4 +1,5 @@
-"""Guard-banded, poisoned buffers for tests that call the C ABI directly (test_gpu_abi_contract.py).
+"""Guard-banded, poisoned buffers for tests that call the C ABI directly (test_gpu_abi_contract.py,
+test_gpu_gemm_contract.py).
 
 The op layer allocates every output and workspace with at::empty, and the caching allocator hands a
 second call the block the first one just freed — still holding the first call's (correct) result.
@@ -16,6 +17,9 @@ caller's choice, so that
     0x3C (finite in every dtype): NaN after the first run means something was read before it was
     written, a difference between the runs means an output depends on what the buffers held.
 Workspaces are sized by the library's own queries, never smaller.
+A matrix with a leading dimension larger than its width (guarded_matrix) ends at its last valid
+element; its gap columns hold NaN when it is an input and must come back untouched when it is an
+output.
 """
 import contextlib
 
@@ -68,6 +72,39 @@ def guarded_copy(t):
     return g
 
 
+class GuardedMatrix(Guarded):
+    """A (rows, cols) matrix with leading dimension `ld` >= cols in a guarded payload of exactly
+    (rows - 1) * ld + cols elements, so the trailing guard starts at the first byte after the last
+    valid element.  `t`: the whole payload (flat); `m`: the (rows, cols) strided view; `gap`: the gap
+    columns [cols, ld) of rows 0 .. rows - 2.  The whole payload, gaps included, is filled with
+    `fill`: 0xFF for an input (write its values through `m`), so that a kernel that reads `ld`
+    elements of a row instead of `cols` poisons its result."""
+
+    def __init__(self, rows, cols, ld, dtype, fill=0):
+        rows, cols, ld = int(rows), int(cols), int(ld)
+        assert rows >= 1 and ld >= cols >= 1
+        super().__init__((rows - 1) * ld + cols, dtype, fill)
+        self.rows, self.cols, self.ld = rows, cols, ld
+        self.m = self.t.as_strided((rows, cols), (ld, 1))
+        self.gap = self.t[:(rows - 1) * ld].view(rows - 1, ld)[:, cols:]
+
+
+def guarded_matrix(rows, cols, ld, dtype, fill=0):
+    return GuardedMatrix(rows, cols, ld, dtype, fill)
+
+
+def guarded_matrix_copy(t, ld):
+    """the 2-d tensor `t`'s values with leading dimension `ld`, NaN in the gaps and behind the last element"""
+    g = GuardedMatrix(t.shape[0], t.shape[1], ld, t.dtype, POISON)
+    g.m.copy_(t)
+    return g
+
+
+def valid(g):
+    """the elements of a guarded buffer a kernel may write: the matrix view, or the whole payload"""
+    return getattr(g, "m", g.t)
+
+
 def bits(t):
     """integer view for bitwise comparisons (NaN == NaN, -0 != +0)"""
     return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
@@ -77,21 +114,31 @@ def bitwise_equal(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
 
 
-def run_poisoned(fn, inputs=(), outputs=(), scratch=(), accum=()):
+def run_poisoned(fn, inputs=(), outputs=(), scratch=(), accum=(), inout=()):
     """Call `fn()` (one entry point through _native.call, on the current stream) twice on the same
     inputs: with `outputs` and `scratch` (Guarded) filled with 0xFF, then with 0x3C; `accum`
-    (accumulating arguments the caller initialises by contract) zeroed before each.  Then, in this
-    order: every guard of every buffer intact, the 0xFF run's outputs all finite, the two runs'
-    outputs bitwise equal.  Returns the outputs' (then the accumulators') values."""
-    runs = []
+    (accumulating arguments the caller initialises by contract) zeroed before each; `inout`, pairs
+    (GuardedMatrix, values) of arguments the entry point reads and overwrites (an aliased side
+    input), set to `values` before each with 0xFF in the gaps.  Then, in this order: every guard of
+    every buffer intact, the 0xFF run's outputs all finite, the two runs' outputs bitwise equal, and
+    the gap columns of every GuardedMatrix among them bitwise what they were on entry, after both
+    runs.  Returns the outputs' (then the accumulators', then the in-out arguments') valid elements."""
+    runs, gaps = [], []
+    written = tuple(outputs) + tuple(accum) + tuple(g for g, _ in inout)
     for byte in (POISON, FINITE):
         for g in tuple(outputs) + tuple(scratch):
             g.fill(byte)
         for g in accum:
             g.fill(0)
+        for g, values in inout:
+            g.fill(POISON)
+            g.m.copy_(values)
+        entry = [bits(g.gap) if hasattr(g, "gap") else None for g in written]
         fn()
-        runs.append([g.t.clone() for g in tuple(outputs) + tuple(accum)])
-    ok = [g.intact() for g in tuple(inputs) + tuple(outputs) + tuple(scratch) + tuple(accum)]
+        runs.append([valid(g).clone() for g in written])
+        gaps.append([(bits(g.gap) == e).all() if e is not None else None for g, e in zip(written, entry)])
+    ok = [g.intact() for g in tuple(inputs) + tuple(outputs) + tuple(scratch) + tuple(accum)
+          + tuple(g for g, _ in inout)]
     torch.cuda.synchronize()
     broken = [i for i, v in enumerate(ok) if not bool(v)]
     assert not broken, f"out-of-bounds write: guard bands of buffers {broken} (inputs, outputs, scratch, accum) changed"
@@ -101,6 +148,10 @@ def run_poisoned(fn, inputs=(), outputs=(), scratch=(), accum=()):
     for i, (a, b) in enumerate(zip(*runs)):
         assert bitwise_equal(a, b), \
             f"output {i} depends on the buffers' contents on entry ({int((bits(a) != bits(b)).sum())} elements differ)"
+    for run, byte in zip(gaps, (POISON, FINITE)):
+        for i, v in enumerate(run):
+            assert v is None or bool(v), \
+                f"output {i}: the columns between its width and its leading dimension were written (0x{byte:02X} run)"
     return runs[0]
 
 
