@@ -239,3 +239,17 @@ def _register_fakes():
         B = img.shape[0]
         return (_e(B, 3, h, w, like=img, dtype=out_dtype), _e(B, h, w, like=img, dtype=torch.int64),
                 _e(B, 1, h, w, like=img, dtype=f32), _e(B, 1, h, w, like=img, dtype=torch.uint8))
+
+    # dclip_eval::* — the fused head evaluation (csrc/headeval.hip), a namespace of its own
+    @reg("dclip_eval::upsample_argmax")
+    def _(logits, H, W):
+        return _e(logits.shape[0], H, W, like=logits, dtype=torch.uint8)
+
+    @reg("dclip_eval::seg_update")
+    def _(logits, labels, ignore_index, cm, ce_sums, want_pred):
+        return _e(*labels.shape, like=logits, dtype=torch.uint8) if want_pred else None
+
+    @reg("dclip_eval::depth_update")
+    def _(pred, target, mask, min_depth, max_depth, clamp_pred, eps, sums, want_up):
+        B, H, W = target.shape
+        return _e(B, 1, H, W, like=pred, dtype=f32) if want_up else None

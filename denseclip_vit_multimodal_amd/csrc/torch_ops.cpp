@@ -896,6 +896,74 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> cityscapes_prepare(const Tensor& img,
     return {out_img, seg, depth, mask};
 }
 
+// ----------------------------------------------------------------------------- fused head evaluation
+Tensor eval_ws(const Tensor& low, int64_t K) {
+    return at::empty({dclip_upsample_eval_ws_bytes((int)low.size(0), (int)K, (int)low.size(2), (int)low.size(3))},
+                     like(low, at::kByte));
+}
+
+// argmax class map u8 (B, H, W) of the resized logits
+Tensor upsample_argmax(const Tensor& logits, int64_t H, int64_t W) {
+    check_gpu(logits, "logits");
+    TORCH_CHECK(logits.dim() == 4, "upsample_argmax: logits (B, K, h, w)");
+    c10::DeviceGuard g(logits.device());
+    Tensor pred = at::empty({logits.size(0), H, W}, like(logits, at::kByte));
+    DCLIP_CALL(dclip_upsample_eval_seg(dt_code(logits.scalar_type()), logits.data_ptr(), (int)logits.size(0),
+                                       (int)logits.size(1), (int)logits.size(2), (int)logits.size(3), nullptr, 0,
+                                       (int)H, (int)W, 0, ptr<uint8_t>(pred), nullptr, nullptr, nullptr, nullptr,
+                                       stream_of(logits)));
+    return pred;
+}
+
+// cm (i64, K x K) += confusion counts, ce_sums (f64[2]) += (sum of -log softmax[label], #valid);
+// the class map when want_pred
+c10::optional<Tensor> seg_update(const Tensor& logits, const Tensor& labels, int64_t ignore_index, Tensor& cm,
+                                 Tensor& ce_sums, bool want_pred) {
+    check_gpu(logits, "logits"); check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
+    TORCH_CHECK(logits.dim() == 4 && labels.dim() == 3 && labels.size(0) == logits.size(0), "seg_update: shapes");
+    const int64_t K = logits.size(1);
+    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, "seg_update: cm must be int64 (K, K)");
+    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2, "seg_update: ce_sums must be float64[2]");
+    c10::DeviceGuard g(logits.device());
+    const int64_t H = labels.size(1), W = labels.size(2);
+    Tensor pred = want_pred ? at::empty({logits.size(0), H, W}, like(logits, at::kByte)) : Tensor();
+    Tensor cnt = at::zeros({1}, like(logits, at::kLong));
+    Tensor ws = eval_ws(logits, K);
+    DCLIP_CALL(dclip_upsample_eval_seg(dt_code(logits.scalar_type()), logits.data_ptr(), (int)logits.size(0), (int)K,
+                                       (int)logits.size(2), (int)logits.size(3), labels.data_ptr(),
+                                       lab_code(labels.scalar_type()), (int)H, (int)W, (int)ignore_index,
+                                       ptr<uint8_t>(pred), ptr<int64_t>(cm), ptr<double>(ce_sums),
+                                       (unsigned long long*)cnt.data_ptr(), ws.data_ptr(), stream_of(logits)));
+    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
+    if (!want_pred) return c10::nullopt;
+    return pred;
+}
+
+// sums (f64[12], dclip.h) += the depth sums of the resized prediction; the resized map (B, 1, H, W) when want_up
+c10::optional<Tensor> depth_update(const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& mask,
+                                   double min_depth, double max_depth, bool clamp_pred, double eps, Tensor& sums,
+                                   bool want_up) {
+    check_gpu(pred, "pred"); check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
+    TORCH_CHECK(pred.dim() == 4 && pred.size(1) == 1, "depth_update: pred (B, 1, h, w)");
+    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == pred.size(0),
+                "depth_update: target (B, H, W) fp32");
+    const bool has_mask = mask.has_value() && mask->defined();
+    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()),
+                "depth_update: mask (B, H, W) uint8");
+    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12, "depth_update: sums must be float64[12]");
+    c10::DeviceGuard g(pred.device());
+    const int64_t H = target.size(1), W = target.size(2);
+    Tensor up = want_up ? at::empty({pred.size(0), 1, H, W}, like(pred, at::kFloat)) : Tensor();
+    Tensor ws = eval_ws(pred, 1);
+    DCLIP_CALL(dclip_upsample_eval_depth(dt_code(pred.scalar_type()), pred.data_ptr(), (int)pred.size(0),
+                                         (int)pred.size(2), (int)pred.size(3), ptr<float>(target), optr<uint8_t>(mask),
+                                         (int)H, (int)W, (float)min_depth, (float)max_depth, clamp_pred ? 1 : 0,
+                                         (float)eps, ptr<float>(up), ptr<double>(sums), ws.data_ptr(),
+                                         stream_of(pred)));
+    if (!want_up) return c10::nullopt;
+    return up;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dclip, m) {
@@ -1011,4 +1079,19 @@ TORCH_LIBRARY_IMPL(dclip, CUDA, m) {
     m.impl("upsample_silog_sums", &upsample_silog_sums);
     m.impl("upsample_silog_grad", &upsample_silog_grad);
     m.impl("cityscapes_prepare", &cityscapes_prepare);
+}
+
+// A namespace of its own: the evaluation ops (headeval.hip) beside the pinned dclip:: set
+TORCH_LIBRARY(dclip_eval, m) {
+    m.def("upsample_argmax(Tensor logits, int H, int W) -> Tensor");
+    m.def("seg_update(Tensor logits, Tensor labels, int ignore_index, Tensor(a!) cm, Tensor(b!) ce_sums, "
+          "bool want_pred) -> Tensor?");
+    m.def("depth_update(Tensor pred, Tensor target, Tensor? mask, float min_depth, float max_depth, bool clamp_pred, "
+          "float eps, Tensor(a!) sums, bool want_up) -> Tensor?");
+}
+
+TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
+    m.impl("upsample_argmax", &upsample_argmax);
+    m.impl("seg_update", &seg_update);
+    m.impl("depth_update", &depth_update);
 }

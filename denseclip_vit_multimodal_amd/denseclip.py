@@ -490,6 +490,27 @@ class DenseCLIP(nn.Module):
             depth = ops.upsample(depth, hw)
         return {"seg": seg, "depth": depth}
 
+    def forward_lowres(self, img):
+        """The eval forward up to, but not including, the final resize to the image:
+        {'seg': (B, K, h, w), 'depth': (B, 1, h, w)}, the heads' own resolution.  `forward(img,
+        return_loss=False)` is ops.upsample of these two maps; evaluate.predict / Evaluator consume
+        them without materialising the resized logits."""
+        if img.is_cuda:
+            self._text_prelaunch(img.device)
+        hcdt = self._hip_heads_dtype(img)
+        if hcdt is not None:
+            seg, depth = self._forward_hip_heads(img, hcdt)
+        else:
+            feats = self.extract_feat(img)
+            self._process_features(feats)
+            param = next(self.neck.parameters()) if self.neck is not None else None
+            if param is not None and feats[0].dtype != param.dtype and feats[0].is_cuda:
+                with torch.autocast("cuda", dtype=feats[0].dtype):
+                    seg, depth = self._heads(feats)
+            else:
+                seg, depth = self._heads(feats)
+        return {"seg": seg, "depth": depth}
+
     def inference(self, img, img_meta, rescale):
         out = self.forward(img, img_metas=img_meta, return_loss=False)
         seg, depth = out.get("seg"), out.get("depth")

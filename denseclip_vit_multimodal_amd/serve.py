@@ -52,3 +52,44 @@ class CapturedForward:
             self.static_in.copy_(img)
         self.graph.replay()
         return self.static_out
+
+
+class CapturedEval:
+    """`evaluate.predict(model, img)` for a fixed input shape / dtype / device, captured into a HIP
+    graph: `forward_lowres`, the fused upsample + argmax of the logits and the resize of the depth.
+    Calling it copies `img` in, replays and returns the captured {'seg': uint8 (B, H, W) class map,
+    'depth': fp32 (B, 1, H, W)} (the SAME tensors every call, as CapturedForward's).  The resized
+    (B, 19, H, W) logits are never materialised, so the graph's pool does not hold them either."""
+
+    def __init__(self, model, example, size=None, warmup=2):
+        from . import evaluate
+        if not example.is_cuda:
+            raise RuntimeError("CapturedEval needs a GPU input (the MI355X path has no CPU fallback)")
+        self.model = model
+        self.size = size
+        self.static_in = example.detach().clone()
+        saved = getattr(model, "graph_text", None)
+        if saved is not None:
+            model.graph_text = "side"  # the text path as a forked branch of this capture (no nested graph)
+        try:
+            side = torch.cuda.Stream(device=example.device)
+            side.wait_stream(torch.cuda.current_stream(example.device))
+            with torch.cuda.stream(side):
+                for _ in range(max(1, warmup)):  # allocator pools, weight casts, library handles
+                    evaluate.predict(model, self.static_in, size)
+            torch.cuda.current_stream(example.device).wait_stream(side)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.static_out = evaluate.predict(model, self.static_in, size)
+        finally:
+            if saved is not None:
+                model.graph_text = saved
+
+    def __call__(self, img):
+        if img.shape != self.static_in.shape or img.dtype != self.static_in.dtype:
+            raise ValueError(f"CapturedEval was captured for {tuple(self.static_in.shape)} {self.static_in.dtype}, "
+                             f"got {tuple(img.shape)} {img.dtype}")
+        if img.data_ptr() != self.static_in.data_ptr():
+            self.static_in.copy_(img)
+        self.graph.replay()
+        return self.static_out

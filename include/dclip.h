@@ -27,6 +27,9 @@
  *   dclip_conv3x3(_wgrad)      ViTFeatureFusionNeck 3x3 ConvBNReLU convs models.py:741-745
  *   dclip_upsample_ce/silog    logits/depth resize + CE / SILog losses denseclip.py:843-868,
  *                              train_denseclip.py:1265-1314, losses.py:21-78
+ *   dclip_upsample_eval_seg/depth  validate()'s resize + argmax / confusion matrix / CE and depth
+ *                              errors, train_denseclip.py:294-684, denseclip/utils.py:109-139,
+ *                              utils/depth_metrics.py:12-88
  *   dclip_im2col               conv1 (16x16, stride 16, no bias) models.py:407,546
  *   dclip_tokens_fwd/bwd       flatten/transpose + CLS + pos add, models.py:548-556
  *   dclip_pos_interp_fwd/bwd   interpolate_pos_encoding models.py:514-540
@@ -367,6 +370,39 @@ int dclip_upsample_ce(int low_dt, const void* logits, int B, int K, int h, int w
 int dclip_upsample_silog(int pass, int low_dt, const void* pred, int B, int h, int w, const float* target,
                          const uint8_t* mask, int H, int W, float eps, float lambd, double* sums, float* grad,
                          float* ws, void* stream);
+
+/* Fused bilinear upsample (align_corners=False) + evaluation of the heads, forward only: the
+ * reference's validate() (train_denseclip.py:294-684: resize :461-467, CE :497, argmax :582, masked
+ * RMSE :589-593) with compute_segmentation_metrics (denseclip/utils.py:109-139) and
+ * compute_depth_errors (utils/depth_metrics.py:12-88), without materialising the resized tensors.
+ * H >= h, W >= w, B*H*W < 2^31.  Additive to ABI 7.
+ *   dclip_upsample_eval_seg:  logits (B, K, h, w) low_dt, K == 19.  pred (nullable): u8 (B, H, W)
+ *       argmax class ids, the lowest index among equal maxima.  labels (nullable): (B, H, W)
+ *       int64 / int32 / uint8 (lab_dt 0 / 1 / 2); pixels whose label is ignore_index or outside
+ *       [0, K) are skipped.  With labels: cm (i64, K x K, row = target, column = prediction)
+ *       += the pixel counts, loss_sum (f64[1]) += sum of -log softmax(up(logits))[label],
+ *       count (u64[1]) += #valid.  Without labels cm, loss_sum and count must be null (pred only;
+ *       ws unused).
+ *   dclip_upsample_eval_depth: pred (B, 1, h, w) low_dt; target f32 (B, H, W); mask u8 (B, H, W) or
+ *       null (all valid).  up (nullable): f32 (B, H, W) resized prediction.  sums (f64[12]) +=
+ *       on mask && min_depth <= target <= max_depth, with p = clamp_pred ? clamp(up, min_depth,
+ *       max_depth) : up, gt = target:
+ *         [0] n  [1] sum (gt-p)^2  [2] sum (log gt - log p)^2  [3] sum |gt-p|/gt  [4] sum (gt-p)^2/gt
+ *         [5..7] #(max(gt/p, p/gt) < 1.25, 1.25^2, 1.25^3)
+ *       on mask alone, with the unclamped up:
+ *         [8] n_mask  [9] sum (gt-up)^2  [10] sum d  [11] sum d^2,  d as in dclip_upsample_silog.
+ * ws: the caller's scratch of dclip_upsample_eval_ws_bytes(B, K, h, w) bytes (K = 1 for depth; a
+ * function of its arguments alone), 8-byte aligned, contents undefined on entry.  Integer counts
+ * are exact; every floating sum has f32 per-pixel terms summed in f64 in a fixed order
+ * (per-workgroup partials in ws, folded in workgroup order by a second launch): two runs are
+ * bitwise equal.  No atomics on global memory.  Stream-ordered: one ws per call in flight.  */
+int64_t dclip_upsample_eval_ws_bytes(int B, int K, int h, int w);
+int dclip_upsample_eval_seg(int low_dt, const void* logits, int B, int K, int h, int w, const void* labels,
+                            int lab_dt, int H, int W, int ignore_index, uint8_t* pred, int64_t* cm,
+                            double* loss_sum, unsigned long long* count, void* ws, void* stream);
+int dclip_upsample_eval_depth(int low_dt, const void* pred, int B, int h, int w, const float* target,
+                              const uint8_t* mask, int H, int W, float min_depth, float max_depth, int clamp_pred,
+                              float eps, float* up, double* sums, void* ws, void* stream);
 
 /* Cityscapes depth + segmentation batch preparation (datasets/cityscapes_depth_seg.py:129-170,
  * 218 and the trainer's RandomCrop / HorizontalFlip / Normalize / ToTensorV2,
