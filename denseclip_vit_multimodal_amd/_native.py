@@ -117,6 +117,10 @@ _SIGS = {
     "dclip_attn_fwd_fp8": [_i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p],
     "dclip_attn_fwd_fp8_workspace": [_i32, _i32, _i32],
     "dclip_gemm_tn_plan": [_i64, _i64, _i64, _c_void_p, _c_void_p],
+    "dclip_adamw_ws_bytes": [_i64],
+    "dclip_adamw_prepare": [_c_void_p, _c_void_p, _c_void_p, _i32, _i64, _c_void_p, _i32, _c_void_p, _c_void_p,
+                            _c_void_p, _i32, _c_void_p],
+    "dclip_adamw_update": [_c_void_p, _c_void_p, _c_void_p, _i32, _i64, _c_void_p, _c_void_p],
 }
 EXPORTED = sorted(list(_SIGS) + ["dclip_last_error", "dclip_abi_version"])
 
@@ -156,6 +160,7 @@ def load(path=None):
         lib.dclip_layernorm_bwd_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_eval_ws_bytes.restype = ctypes.c_int64
+        lib.dclip_adamw_ws_bytes.restype = ctypes.c_int64
         # kernel-variant knobs for A/B runs: DCLIP_OPTIONS="id=value,..." (DCLIP_OPT_* ids of dclip.h)
         for kv in filter(None, os.environ.get("DCLIP_OPTIONS", "").split(",")):
             k, v = kv.split("=")

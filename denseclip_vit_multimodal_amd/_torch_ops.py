@@ -253,3 +253,12 @@ def _register_fakes():
     def _(pred, target, mask, min_depth, max_depth, clamp_pred, eps, sums, want_up):
         B, H, W = target.shape
         return _e(B, 1, H, W, like=pred, dtype=f32) if want_up else None
+
+    # dclip_optim::* — the native AdamW step (csrc/optim.hip), a namespace of its own
+    @reg("dclip_optim::adamw_prepare")
+    def _(desc, desc_host, grads, tiles, hp, found_inf, state, with_norm):
+        return None
+
+    @reg("dclip_optim::adamw_update")
+    def _(desc, desc_host, grads, tiles, state):
+        return None

@@ -964,6 +964,62 @@ c10::optional<Tensor> depth_update(const Tensor& pred, const Tensor& target, con
     return up;
 }
 
+// ----------------------------------------------------------------------------- optimizer
+// dclip_adamw_* (optim.hip): desc (n, 12) int64 on the GPU, desc_host the same table on the CPU,
+// grads the f32 gradients in entry order (an undefined / empty tensor: no gradient this step)
+std::vector<const void*> adamw_args(const Tensor& desc, const Tensor& desc_host, at::TensorList grads,
+                                    const Tensor& state) {
+    check_gpu(desc, "desc"); check_gpu(state, "state");
+    TORCH_CHECK(desc.scalar_type() == at::kLong && desc.dim() == 2 && desc.size(1) == DCLIP_ADAMW_DESC_WORDS,
+                "adamw: desc must be an (n, ", DCLIP_ADAMW_DESC_WORDS, ") int64 tensor");
+    TORCH_CHECK(desc_host.defined() && desc_host.is_cpu() && desc_host.is_contiguous() &&
+                    desc_host.scalar_type() == at::kLong && desc_host.sizes() == desc.sizes(),
+                "adamw: desc_host must be the CPU copy of desc");
+    TORCH_CHECK((int64_t)grads.size() == desc.size(0), "adamw: ", desc.size(0), " entries but ", grads.size(),
+                " gradients");
+    TORCH_CHECK(state.scalar_type() == at::kFloat && state.numel() >= DCLIP_ADAMW_STATE_HEAD, "adamw: state must be f32");
+    std::vector<const void*> g(grads.size());
+    const int64_t* dh = (const int64_t*)desc_host.data_ptr();
+    for (size_t i = 0; i < grads.size(); ++i) {
+        const Tensor& t = grads[i];
+        if (!t.defined() || t.numel() == 0) { g[i] = nullptr; continue; }
+        TORCH_CHECK(t.is_cuda() && t.device() == desc.device() && t.scalar_type() == at::kFloat &&
+                        t.is_non_overlapping_and_dense() &&
+                        t.numel() == dh[i * DCLIP_ADAMW_DESC_WORDS + 5] * dh[i * DCLIP_ADAMW_DESC_WORDS + 6],
+                    "adamw: gradient ", i, " must be a dense f32 GPU tensor of its parameter's size (and layout)");
+        g[i] = t.data_ptr();
+    }
+    return g;
+}
+
+void adamw_prepare(const Tensor& desc, const Tensor& desc_host, at::TensorList grads, int64_t tiles, const Tensor& hp,
+                   const c10::optional<Tensor>& found_inf, Tensor& state, bool with_norm) {
+    const std::vector<const void*> g = adamw_args(desc, desc_host, grads, state);
+    check_gpu(hp, "hp"); check_opt(found_inf, "found_inf");
+    TORCH_CHECK(hp.scalar_type() == at::kFloat && hp.dim() == 2 && hp.size(1) == DCLIP_ADAMW_HP_FLOATS,
+                "adamw_prepare: hp must be (rows, ", DCLIP_ADAMW_HP_FLOATS, ") f32");
+    TORCH_CHECK(state.numel() == DCLIP_ADAMW_STATE_HEAD + hp.size(0) * DCLIP_ADAMW_STATE_ROW_FLOATS,
+                "adamw_prepare: state must hold ", DCLIP_ADAMW_STATE_HEAD, " + ", DCLIP_ADAMW_STATE_ROW_FLOATS,
+                " f32 per hp row");
+    const bool has_ext = found_inf.has_value() && found_inf->defined();
+    TORCH_CHECK(!has_ext || (found_inf->scalar_type() == at::kFloat && found_inf->numel() == 1),
+                "adamw_prepare: found_inf must be one f32");
+    c10::DeviceGuard guard(desc.device());
+    Tensor ws = with_norm ? at::empty({dclip_adamw_ws_bytes(tiles)}, like(desc, at::kByte)) : Tensor();
+    DCLIP_CALL(dclip_adamw_prepare((const int64_t*)desc.data_ptr(), (const int64_t*)desc_host.data_ptr(), g.data(),
+                                   (int)desc.size(0), tiles, ptr<float>(hp), (int)hp.size(0), optr<float>(found_inf),
+                                   ptr<float>(state), with_norm ? ws.data_ptr() : nullptr, with_norm ? 1 : 0,
+                                   stream_of(desc)));
+}
+
+void adamw_update(const Tensor& desc, const Tensor& desc_host, at::TensorList grads, int64_t tiles,
+                  const Tensor& state) {
+    const std::vector<const void*> g = adamw_args(desc, desc_host, grads, state);
+    c10::DeviceGuard guard(desc.device());
+    DCLIP_CALL(dclip_adamw_update((const int64_t*)desc.data_ptr(), (const int64_t*)desc_host.data_ptr(), g.data(),
+                                  (int)desc.size(0), tiles, ptr<float>(state), stream_of(desc)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dclip, m) {
@@ -1094,4 +1150,17 @@ TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
     m.impl("upsample_argmax", &upsample_argmax);
     m.impl("seg_update", &seg_update);
     m.impl("depth_update", &depth_update);
+}
+
+// The native optimizer step (optim.hip).  p, m, v and the 16-bit copies are written through the
+// addresses in desc (as dclip::weight_refresh writes its copies); state is the declared output.
+TORCH_LIBRARY(dclip_optim, m) {
+    m.def("adamw_prepare(Tensor desc, Tensor desc_host, Tensor[] grads, int tiles, Tensor hp, Tensor? found_inf, "
+          "Tensor(a!) state, bool with_norm) -> ()");
+    m.def("adamw_update(Tensor desc, Tensor desc_host, Tensor[] grads, int tiles, Tensor state) -> ()");
+}
+
+TORCH_LIBRARY_IMPL(dclip_optim, CUDA, m) {
+    m.impl("adamw_prepare", &adamw_prepare);
+    m.impl("adamw_update", &adamw_update);
 }

@@ -549,6 +549,10 @@ def _stamp_stepped_params(opt, *_):
     for group in opt.param_groups:
         for p in group["params"]:
             p.__dict__["_dclip_step"] = _STEP[0]
+    if getattr(opt, "writes_weight_copies", False):
+        # train.FusedAdamW: its update kernel wrote the copies; no weight_refresh launch after it
+        opt.restamp_weight_copies()
+        return
     if EAGER_WEIGHT_REFRESH:
         refresh_weight_copies([p for group in opt.param_groups for p in group["params"]])
 
@@ -575,17 +579,12 @@ LN_DY_LP_FP16 = True
 _REFRESH_DESC = {}  # (device, dtype) -> (key, device descriptor, tiles, pinned host copy)
 
 
-def refresh_weight_copies(params):
-    """Refresh, in place, the plain and transposed compute-dtype copies WEIGHTS holds for these
-    fp32 parameters (the entries earlier forwards / backwards created), and re-stamp them valid.
-    The copies keep their storage, so the device descriptor of the launch is built once and
-    reused while the set of copies is unchanged.  A no-op for parameters without cached copies;
-    derived layouts (get_with) stay lazy.  During stream capture (a whole train step captured into
-    a graph, train.CapturedTrainStep) the launch is captured with the descriptor an eager step
-    built, so every replay refreshes the copies after its optimizer step."""
-    if not torch.cuda.is_available():
-        return
-    capturing = torch.cuda.is_current_stream_capturing()
+def collect_weight_copies(params):
+    """The cached plain / transposed compute-dtype copies of these fp32 parameters that one launch
+    can rewrite in place: {(device, dtype): [(cache, dtype, w, plain or None, transposed or None,
+    stamp, rows, cols, p)]}, in the parameters' order.  Eligible: a contiguous, 16-byte aligned
+    fp32 GPU parameter; copies of the expected shape and dtype, contiguous, 16-byte aligned, not
+    the parameter's own storage.  (refresh_weight_copies and train.FusedAdamW share these rules.)"""
     groups = {}
     for p in params:
         cache = p.__dict__.get("_dclip_cache")
@@ -609,31 +608,57 @@ def refresh_weight_copies(params):
                 vt = None
             if vp is None and vt is None:
                 continue
-            groups.setdefault((w.device, dt), []).append((cache, dt, w, vp, vt, stamp, rows, cols))
-    for (dev, dt), items in groups.items():
-        key = tuple((w.data_ptr(), 0 if vp is None else vp.data_ptr(), 0 if vt is None else vt.data_ptr(), r, c)
-                    for _, _, w, vp, vt, _, r, c in items)
-        ent = _REFRESH_DESC.get((dev, dt))
-        if capturing and (ent is None or ent[0] != key):
-            # a new descriptor needs a host -> device copy; replays without the refresh would read
-            # stale copies: the set of copies must be the one an eager step already refreshed
-            raise RuntimeError("refresh_weight_copies: the cached weight copies changed since the last eager "
-                               "optimizer step; run one eager step before capturing the train step")
-        if ent is None or ent[0] != key:
-            table, tiles = [], 0
-            for src, dp, dtp, r, c in key:
-                tc = (c + 63) // 64
-                table.append([src, dp, dtp, r, c, tiles, tc, 0])
-                tiles += ((r + 63) // 64) * tc
-            host = torch.tensor(table, dtype=torch.int64).pin_memory()
-            desc = host.to(dev, non_blocking=True)
-            ent = _REFRESH_DESC[(dev, dt)] = (key, desc, tiles, host)
-        D().weight_refresh(ent[1], ent[2], dt)
-        for cache, dt_, w, vp, vt, stamp, _, _ in items:
-            if vp is not None:
-                cache[(dt_, False)] = (stamp, vp)
-            if vt is not None:
-                cache[(dt_, True)] = (stamp, vt)
+            groups.setdefault((w.device, dt), []).append((cache, dt, w, vp, vt, stamp, rows, cols, p))
+    return groups
+
+
+def restamp_weight_copies(items, plain=True, transposed=True):
+    """Mark the collected copies valid for their parameter as it is now (after they were rewritten)."""
+    for cache, dt_, _, vp, vt, _, _, _, p in items:
+        stamp = _Cast.stamp(p)
+        if vp is not None and plain:
+            cache[(dt_, False)] = (stamp, vp)
+        if vt is not None and transposed:
+            cache[(dt_, True)] = (stamp, vt)
+
+
+def _launch_weight_refresh(dev, dt, items, capturing):
+    key = tuple((w.data_ptr(), 0 if vp is None else vp.data_ptr(), 0 if vt is None else vt.data_ptr(), r, c)
+                for _, _, w, vp, vt, _, r, c, _ in items)
+    ent = _REFRESH_DESC.get((dev, dt))
+    if capturing and (ent is None or ent[0] != key):
+        # a new descriptor needs a host -> device copy; replays without the refresh would read
+        # stale copies: the set of copies must be the one an eager step already refreshed
+        raise RuntimeError("refresh_weight_copies: the cached weight copies changed since the last eager "
+                           "optimizer step; run one eager step before capturing the train step")
+    if ent is None or ent[0] != key:
+        table, tiles = [], 0
+        for src, dp, dtp, r, c in key:
+            tc = (c + 63) // 64
+            table.append([src, dp, dtp, r, c, tiles, tc, 0])
+            tiles += ((r + 63) // 64) * tc
+        host = torch.tensor(table, dtype=torch.int64).pin_memory()
+        desc = host.to(dev, non_blocking=True)
+        ent = _REFRESH_DESC[(dev, dt)] = (key, desc, tiles, host)
+    D().weight_refresh(ent[1], ent[2], dt)
+
+
+def refresh_weight_copies(params):
+    """Refresh, in place, the plain and transposed compute-dtype copies WEIGHTS holds for these
+    fp32 parameters (the entries earlier forwards / backwards created), and re-stamp them valid.
+    The copies keep their storage, so the device descriptor of the launch is built once and
+    reused while the set of copies is unchanged.  A no-op for parameters without cached copies;
+    derived layouts (get_with) stay lazy.  During stream capture (a whole train step captured into
+    a graph, train.CapturedTrainStep) the launch is captured with the descriptor an eager step
+    built, so every replay refreshes the copies after its optimizer step.
+    Three parts — collect_weight_copies, the launch, restamp_weight_copies — of which
+    train.FusedAdamW, whose update kernel writes the copies itself, uses the first and the last."""
+    if not torch.cuda.is_available():
+        return
+    capturing = torch.cuda.is_current_stream_capturing()
+    for (dev, dt), items in collect_weight_copies(params).items():
+        _launch_weight_refresh(dev, dt, items, capturing)
+        restamp_weight_copies(items)
 
 
 from torch.optim.optimizer import register_optimizer_step_post_hook  # noqa: E402

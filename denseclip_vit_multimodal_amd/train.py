@@ -14,6 +14,8 @@ step (its CLI, logging, metrics and checkpointing are out of scope — DESIGN.md
 Mode "R" is the reference regime (backbone + text frozen); mode "F" also trains the ViT,
 which exercises the HIP backward kernels (the north star's roofline applies there).
 """
+import contextlib
+
 import torch
 import torch.nn.functional as F
 
@@ -208,7 +210,19 @@ class GradAllReduce(torch.nn.Module):
         # so the GEMMs launched between the first bucket's launch and _finish take the claims walk
         self.gemm_walk_under_collectives = 1
         self._pending = None
+        self._sync = True  # False inside no_sync()
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for _, p in params]
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        """Gradient accumulation, as DistributedDataParallel.no_sync(): backwards run inside it add
+        to the local gradients only — the hooks neither count arrivals nor launch a collective.
+        The first backward outside it reduces the accumulated sums (train_step_accum)."""
+        prev, self._sync = self._sync, False
+        try:
+            yield
+        finally:
+            self._sync = prev
 
     def forward(self, *args, **kwargs):
         if self._buffers_to_sync and self._world > 1:
@@ -243,6 +257,8 @@ class GradAllReduce(torch.nn.Module):
                 st["works"].append((d.all_reduce(g, async_op=True), g))
 
     def _on_grad(self, p):
+        if not self._sync:
+            return
         if self._pending is None:
             self._pending = {"ready": [0] * len(self._buckets), "launched": [False] * len(self._buckets), "works": [],
                              "next": 0, "walk": None}
@@ -274,16 +290,275 @@ class GradAllReduce(torch.nn.Module):
         self._pending = None
 
 
-def make_optimizer(params, fused=None, capturable=False):
+def make_optimizer(params, fused=None, capturable=False, native=False, clip_grad_norm=None):
     """AdamW(lr 2e-5, weight decay 0.01) as the reference trainer builds it (train_denseclip.py:1061),
     fused on GPU parameters; capturable=True keeps its step counts on the device (required by
-    CapturedTrainStep)."""
+    CapturedTrainStep).  native=True: FusedAdamW, this package's own multi-tensor step (always
+    capturable), which clips to a global norm of clip_grad_norm when that is given."""
     params = list(params)
+    if native:
+        return FusedAdamW(params, lr=2e-5, weight_decay=0.01, max_norm=clip_grad_norm)
+    if clip_grad_norm is not None:
+        raise ValueError("make_optimizer: clip_grad_norm belongs to the native optimizer (native=True); with a torch "
+                         "optimizer pass it to train_step_accum")
     if fused is None:
         fused = all(p.is_cuda for p in params)
     if capturable:
         return torch.optim.AdamW(params, lr=2e-5, weight_decay=0.01, fused=fused, capturable=True)
     return torch.optim.AdamW(params, lr=2e-5, weight_decay=0.01, fused=fused)
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW's step as this package's own two HIP passes (csrc/optim.hip, the arithmetic
+    in include/dclip.h), with what the trainer's YAML asks for around it:
+      * max_norm         torch.nn.utils.clip_grad_norm_ over ALL groups' gradients, applied as a
+                         factor on load (the gradients are never rewritten); the threshold is
+                         the first group's
+      * set_inv_accum    the 1/k of a k-micro-batch accumulation, applied the same way
+      * group["lr"]      a float, or a 1-element device tensor that a scheduler may rewrite between
+                         replays of a captured step (the kernels read lr from device memory)
+      * found_inf        honoured as torch's fused optimizers honour it (step_unless_nonfinite);
+                         with check_grads the norm pass also flags non-finite gradients
+      * the 16-bit plain and transposed weight copies of ops.WEIGHTS are written by the update
+        itself (no weight_refresh launch follows), under ops.collect_weight_copies' rules.
+    GPU fp32 parameters only (no CPU fallback).  One step count for the whole optimizer, on the
+    device; it does not advance on a skipped step.  state_dict() / load_state_dict() interchange
+    with torch.optim.AdamW: 'step' (f32), 'exp_avg', 'exp_avg_sq' per parameter — loading per-
+    parameter steps that differ raises.  No host synchronisation in step().  amsgrad / maximize
+    are not supported.
+
+    last_total_norm / last_found_inf: 0-dim device tensors of the last prepared step (views of the
+    optimizer's state: clone them to keep a value).
+
+    The gradient addresses go to the kernels as launch arguments, 256 per launch: nothing
+    the host could overwrite while an earlier step's launch still reads it."""
+
+    writes_weight_copies = True  # ops' step hook: no weight_refresh after this optimizer
+
+    def __init__(self, params, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_norm=None):
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0) or eps < 0 or weight_decay < 0:
+            raise ValueError(f"FusedAdamW: invalid betas {betas}, eps {eps} or weight_decay {weight_decay}")
+        # every key a torch.optim.AdamW group carries, so that state dicts load in both directions
+        defaults = dict(torch.optim.AdamW([torch.zeros(1)]).defaults)
+        defaults.update(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, fused=True, capturable=True,
+                        max_norm=max_norm)
+        super().__init__(params, defaults)
+        self._device = None
+        for g in self.param_groups:
+            for p in g["params"]:
+                if not p.is_cuda or p.dtype != torch.float32:
+                    raise RuntimeError(f"FusedAdamW: GPU fp32 parameters only (got {tuple(p.shape)} {p.dtype} on "
+                                       f"{p.device}); the MI355X path has no CPU fallback")
+                if self._device is None:
+                    self._device = p.device
+                elif p.device != self._device:
+                    raise RuntimeError("FusedAdamW: all parameters on one device")
+        self._inv_accum = 1.0
+        self._hp = self._st = None   # device hyper-parameter table / state (include/dclip.h)
+        self._hp_host = []           # the floats last written to the table, per row
+        self._desc = None            # (key, device descriptor, host descriptor, tiles)
+        self._prepared = None        # (desc, grads, copies, [(p, p.grad)]) between prepare() and step()
+        self._stepped = None         # copies of the last step, for the hook's re-stamp
+
+    # ------------------------------------------------------------------ device scalars
+    def _buffers(self):
+        rows = len(self.param_groups)
+        if self._st is None or self._hp.shape[0] != rows:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdamW: run one eager step before capturing the train step")
+            step = None if self._st is None else self._st[3].clone()
+            self._hp = torch.zeros(rows, 8, dtype=torch.float32, device=self._device)
+            self._st = torch.zeros(8 + 12 * rows, dtype=torch.float32, device=self._device)
+            if step is not None:
+                self._st[3] = step
+            self._hp_host = [None] * rows
+        return self._hp, self._st
+
+    @property
+    def last_total_norm(self):
+        return self._buffers()[1][0]
+
+    @property
+    def last_found_inf(self):
+        return self._buffers()[1][2]
+
+    @property
+    def step_count(self):
+        """0-dim device f32: the number of steps applied"""
+        return self._buffers()[1][3]
+
+    def set_inv_accum(self, inv_accum):
+        """1 / k for gradients summed over k micro-batches (train_step_accum)"""
+        self._inv_accum = float(inv_accum)
+
+    def _sync_hp(self):
+        """Bring the device table up to the groups' values: a changed float is written by a fill
+        (a kernel argument: no host buffer, no synchronisation); a tensor lr is copied on the device."""
+        hp, _ = self._buffers()
+        capturing = torch.cuda.is_current_stream_capturing()
+        for r, g in enumerate(self.param_groups):
+            if g.get("amsgrad") or g.get("maximize"):
+                raise RuntimeError("FusedAdamW: amsgrad / maximize are not supported")
+            lr = g["lr"]
+            vals = [None if torch.is_tensor(lr) else float(lr), 1.0 - float(g["betas"][0]), 1.0 - float(g["betas"][1]),
+                    float(g["eps"]), float(g["weight_decay"]), float(g.get("max_norm") or 0.0), self._inv_accum, 0.0]
+            old = self._hp_host[r]
+            for k, v in enumerate(vals):
+                if v is None:
+                    if not lr.is_cuda or lr.numel() != 1:
+                        raise RuntimeError("FusedAdamW: a tensor lr must be a 1-element GPU tensor")
+                    hp[r, 0:1].copy_(lr.detach().reshape(1))
+                elif old is None or old[k] != v:
+                    if capturing:
+                        raise RuntimeError(f"FusedAdamW: hyper-parameter {k} of group {r} changed under stream capture "
+                                           "(use a 1-element device tensor for a scheduled lr; run one eager step "
+                                           "before capturing the train step)")
+                    hp[r, k].fill_(v)
+            self._hp_host[r] = vals
+
+    # ------------------------------------------------------------------ descriptor
+    def _collect(self):
+        """Entries for the parameters that have a gradient: (descriptor, gradients, copy items)."""
+        from . import ops
+        entries = []
+        for r, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                gr = p.grad
+                if gr is None or p.numel() == 0:
+                    continue
+                if gr.is_sparse or gr.dtype != torch.float32 or gr.device != p.device:
+                    raise RuntimeError(f"FusedAdamW: dense fp32 gradients on the parameter's device only "
+                                       f"(parameter {tuple(p.shape)})")
+                w = p.detach()
+                if not (w.is_contiguous() or (w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last))):
+                    raise RuntimeError(f"FusedAdamW: parameter {tuple(p.shape)} is not dense in memory")
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    st["exp_avg"] = torch.zeros_like(w, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(w, memory_format=torch.preserve_format)
+                m, v = st["exp_avg"], st["exp_avg_sq"]
+                if m.stride() != w.stride() or v.stride() != w.stride():
+                    raise RuntimeError(f"FusedAdamW: the moments of parameter {tuple(p.shape)} have another layout")
+                if gr.stride() != w.stride():  # elementwise over the storage: the same layout as p
+                    gr = torch.empty_like(w, memory_format=torch.preserve_format).copy_(gr)
+                entries.append((r, p, w, gr, m, v))
+        if not entries:
+            return None
+        copies = {}
+        for items in ops.collect_weight_copies([e[1] for e in entries]).values():
+            for it in items:  # a parameter with copies in both dtypes: the first (bf16) is written here,
+                copies.setdefault(id(it[-1]), it)  # the other keeps a stale stamp and is rebuilt on use
+        key, mine = [], []
+        for r, p, w, gr, m, v in entries:
+            it = copies.get(id(p))
+            rows = w.shape[0] if w.dim() else 1
+            cols = w.numel() // rows
+            vp = vt = None
+            dt = 0
+            if it is not None:
+                _, tdt, _, vp, vt, stamp, _, _, _ = it
+                dt = 2 if tdt == torch.bfloat16 else 1  # DCLIP_BF16 / DCLIP_F16
+                cache = it[0]
+                # a copy that was stale BEFORE the step stays stale if the step is skipped on the
+                # device: only copies valid now are re-stamped (steady state: all of them)
+                mine.append((it, vp is not None and cache[(tdt, False)][0] == stamp,
+                             vt is not None and cache[(tdt, True)][0] == stamp))
+            key.append((w.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if vp is None else vp.data_ptr(),
+                        0 if vt is None else vt.data_ptr(), rows, cols, r, dt))
+        key = tuple(key)
+        if self._desc is None or self._desc[0] != key:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdamW: the parameters, moments or cached weight copies changed since the last "
+                                   "eager optimizer step; run one eager step before capturing the train step")
+            table, tiles = [], 0
+            for pp, mp, vp_, dp, dtp, rows, cols, r, dt in key:
+                tcn = (cols + 63) // 64 if dtp else 0
+                table.append([pp, mp, vp_, dp, dtp, rows, cols, tiles, tcn, r, dt, 0])
+                tiles += ((rows + 63) // 64) * tcn if tcn else (rows * cols + 4095) // 4096
+            host = torch.tensor(table, dtype=torch.int64)
+            self._desc = (key, host.to(self._device), host, tiles)
+        return self._desc, [e[3] for e in entries], mine, [(e[1], e[1].grad) for e in entries]
+
+    # ------------------------------------------------------------------ the step
+    @torch.no_grad()
+    def prepare(self, found_inf=None, check_grads=False):
+        """First half of a step: the gradient norm pass (when a group clips, or check_grads) and the
+        fold that writes the step's scalars — total norm, clip coefficient, found_inf (the sum of
+        squares is not finite, or `found_inf` is non-zero), the bias corrections of the step count
+        this step will have.  The next step() applies exactly this prepared step — unless
+        zero_grad() ran or a parameter's .grad is another tensor by then: a prepared step that went
+        stale is dropped and step() prepares afresh.  Nothing is counted here: the update commits
+        the step count, so preparing twice, or without a step(), counts no step.  False when no
+        parameter has a gradient."""
+        got = self._collect()
+        if got is None:
+            self._prepared = None
+            return False
+        desc, grads, copies, live = got
+        self._sync_hp()
+        from . import ops
+        ops.D()
+        if found_inf is not None:
+            found_inf = found_inf.detach().to(device=self._device, dtype=torch.float32).reshape(1)
+        with_norm = bool(check_grads) or any(g.get("max_norm") for g in self.param_groups)
+        torch.ops.dclip_optim.adamw_prepare(desc[1], desc[2], grads, desc[3], self._hp, found_inf, self._st, with_norm)
+        self._prepared = (desc, grads, copies, live)
+        return True
+
+    def zero_grad(self, set_to_none=True):
+        self._prepared = None  # a prepared step does not outlive its gradients
+        super().zero_grad(set_to_none=set_to_none)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._prepared is not None and any(p.grad is not g for p, g in self._prepared[3]):
+            self._prepared = None  # prepared on gradients that have been replaced since
+        if self._prepared is None and not self.prepare(getattr(self, "found_inf", None)):
+            self._stepped = None
+            return loss
+        desc, grads, copies, _ = self._prepared
+        self._prepared = None
+        torch.ops.dclip_optim.adamw_update(desc[1], desc[2], grads, desc[3], self._st)
+        self._stepped = copies
+        return loss
+
+    def restamp_weight_copies(self):
+        """Called by ops' optimizer-step hook once the parameters carry the new step stamp: the
+        copies this step wrote (or, on a skipped step, left equal to their unchanged parameter)
+        are valid for the next forward."""
+        from . import ops
+        for it, plain, transposed in self._stepped or ():
+            ops.restamp_weight_copies([it], plain, transposed)
+        self._stepped = None
+
+    # ------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        sd = super().state_dict()
+        if sd["state"]:
+            step = self.step_count
+            sd["state"] = {i: {"step": step.clone(), **s} for i, s in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        # checked on the incoming dict, before anything of this optimizer changes
+        steps = [float(s["step"]) for s in state_dict["state"].values() if "step" in s]
+        if steps and min(steps) != max(steps):
+            raise ValueError("FusedAdamW.load_state_dict: the per-parameter step counts differ "
+                             f"({min(steps):g} .. {max(steps):g}); this optimizer keeps one")
+        keep = [g.get("max_norm") for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for g, mn in zip(self.param_groups, keep):
+            g.setdefault("max_norm", mn)
+            g["fused"], g["capturable"] = True, True
+        for s in self.state.values():
+            s.pop("step", None)
+        self._buffers()[1][3] = steps[0] if steps else 0.0
+        self._hp_host = [None] * len(self.param_groups)
+        self._desc = self._prepared = None
 
 
 def nonfinite_flag(opt, loss, check_grads=True):
@@ -293,6 +568,20 @@ def nonfinite_flag(opt, loss, check_grads=True):
     catches an fp16 overflow in a backward whose loss stayed finite (the neck / heads run on one
     power-of-two gradient scale, ops.HeadScale)."""
     flag = (~torch.isfinite(loss.detach().reshape(-1)[0])).to(torch.float32)
+    if isinstance(opt, FusedAdamW):
+        # the gradients' finiteness comes from the optimizer's own norm pass (one read of the
+        # gradients, shared with the clipping): the loss flag goes in as its external flag, after
+        # the MAX-reduction — the gradients are identical on every rank after the all-reduce, so
+        # their flag needs no collective.  opt.step() then applies the step prepared here.
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        if opt.prepare(found_inf=flag, check_grads=check_grads):
+            flag = opt.last_found_inf
+        if check_grads:
+            from . import ops
+            ops.watch_fp16_overflow(flag)
+        return flag
     if check_grads:
         grads = [p.grad for g in opt.param_groups for p in g["params"] if p.grad is not None]
         if grads:
@@ -345,6 +634,89 @@ def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1):
     return loss.detach()
 
 
+def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silog_weight=0.1, clip_grad_norm=None):
+    """One optimizer step on the mean gradient of k = len(micro_batches) micro-batches
+    (training.grad_accum_steps, train_denseclip.py:1154, 1314, 1356-1358): zero_grad, then forward /
+    loss / backward per micro-batch — every one but the last inside the wrapper's no_sync(), so the
+    data-parallel all-reduce runs once, on the accumulated gradients — then one step.
+    A torch optimizer gets each loss scaled by 1/k, as the reference does, and, with clip_grad_norm,
+    torch.nn.utils.clip_grad_norm_ before the step.  FusedAdamW gets the unscaled sums and applies
+    1/k (set_inv_accum) and the clipping (its groups' max_norm, or clip_grad_norm when given)
+    inside its kernels; both factors are set for this step and restored after it.  Returns the mean loss (no host sync).
+
+    Departure from the reference: a non-finite micro-batch loss poisons the mean loss and the
+    accumulated gradients, and the WHOLE step is then skipped on the device
+    (step_unless_nonfinite); the reference skips only that micro-batch's backward, on a host check
+    of its loss (train_denseclip.py:1323), and steps on the rest."""
+    k = len(micro_batches)
+    if k < 1:
+        raise ValueError("train_step_accum: at least one micro-batch")
+    native = isinstance(opt, FusedAdamW)
+    opt.zero_grad(set_to_none=True)
+    total = None
+    for i, (img, seg, depth, mask) in enumerate(micro_batches):
+        hold = i < k - 1 and hasattr(model, "no_sync")
+        with (model.no_sync() if hold else contextlib.nullcontext()):
+            out = model(img, gt_semantic_seg=seg, gt_depth=depth, return_loss=True)
+            loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight)
+            (loss if native else loss / k).backward()
+        total = loss.detach() if total is None else total + loss.detach()
+    mean = total / k
+    if not native:
+        if clip_grad_norm is not None:
+            torch.nn.utils.clip_grad_norm_([p for g in opt.param_groups for p in g["params"]], clip_grad_norm)
+        step_unless_nonfinite(opt, mean, check_grads=fp16_backward(model, img))
+        return mean
+    # the two factors hold for this step only: a later train_step with the same optimizer sees 1
+    # and its own max_norm again (the device table is written when a prepare finds a changed value)
+    saved = (opt._inv_accum, [g.get("max_norm") for g in opt.param_groups])
+    opt.set_inv_accum(1.0 / k)
+    if clip_grad_norm is not None:
+        for g in opt.param_groups:
+            g["max_norm"] = clip_grad_norm
+    try:
+        step_unless_nonfinite(opt, mean, check_grads=fp16_backward(model, img))
+    finally:
+        opt.set_inv_accum(saved[0])
+        for g, mn in zip(opt.param_groups, saved[1]):
+            g["max_norm"] = mn
+    return mean
+
+
+def trainer_config(cfg):
+    """What the reference trainer reads from training.* around the step (train_denseclip.py:1057-1069,
+    1154-1155), with its defaults: {'grad_accum_steps', 'clip_grad_norm', 'optimizer' (its kwargs,
+    'type' kept), 'scheduler' (the config make_scheduler takes), 'epochs'}."""
+    tr = (cfg or {}).get("training", {}) or {}
+    epochs = tr.get("epochs")
+    sched = dict(tr.get("scheduler") or {"type": "CosineAnnealingLR", "T_max": epochs, "eta_min": 1e-6})
+    clip = tr.get("clip_grad_norm", None)
+    return {"grad_accum_steps": int(tr.get("grad_accum_steps", 1)),
+            "clip_grad_norm": None if clip is None else float(clip),
+            "optimizer": dict(tr.get("optimizer") or {"type": "AdamW", "lr": 0.0001, "weight_decay": 0.0001}),
+            "scheduler": sched, "epochs": epochs}
+
+
+def make_scheduler(opt, cfg):
+    """The reference's LR scheduler (train_denseclip.py:1066-1083) from a trainer YAML:
+    CosineAnnealingLR (T_max defaults to training.epochs), StepLR, or 'poly' = PolynomialLR
+    (total_iters defaults to the epochs, power to 0.9); stepped once per epoch.  An unknown type
+    raises (the reference warns and trains at a constant rate)."""
+    tc = trainer_config(cfg)
+    sc = dict(tc["scheduler"])
+    kind = str(sc.pop("type", "CosineAnnealingLR")).lower()
+    if kind == "cosineannealinglr":
+        sc.setdefault("T_max", tc["epochs"])
+        return torch.optim.lr_scheduler.CosineAnnealingLR(opt, **sc)
+    if kind == "steplr":
+        return torch.optim.lr_scheduler.StepLR(opt, **sc)
+    if kind == "poly":
+        sc.setdefault("total_iters", tc["epochs"])
+        sc.setdefault("power", 0.9)
+        return torch.optim.lr_scheduler.PolynomialLR(opt, **sc)
+    raise ValueError(f"make_scheduler: unknown scheduler type {kind!r} (CosineAnnealingLR, StepLR or poly)")
+
+
 class CapturedTrainStep:
     """train_step captured once into one HIP graph and replayed: forward, loss, backward, the
     non-finite check and the fused AdamW update (skipped on the device when the flag is set), and
@@ -363,17 +735,33 @@ class CapturedTrainStep:
     capture): its replays equal eager steps run with ops.FP16_DELAYED_SCALE = False bit for bit
     (tests/test_gpu_determinism.py; the step is bitwise reproducible since the fixed-order loss
     folds of ABI 7), and measured slower than the eager delayed-scale step (137.5 vs 135.1 ms,
-    DESIGN.md §5), so the bench's fp16 line stays eager."""
+    DESIGN.md §5), so the bench's fp16 line stays eager.
 
-    def __init__(self, model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, warmup=3):
+    FusedAdamW is accepted like a capturable torch AdamW; a learning rate held in a 1-element device
+    tensor is read by every replay.  accum_steps=k: `batch` is a sequence of k micro-batches and the
+    one graph holds k forward / backward passes and one update (train_step_accum)."""
+
+    def __init__(self, model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, warmup=3, accum_steps=1):
         if isinstance(model, (torch.nn.parallel.DistributedDataParallel, GradAllReduce)):
             raise RuntimeError("CapturedTrainStep: one process only (the data-parallel all-reduce hooks are not captured)")
         if not all(g.get("fused") and g.get("capturable") for g in opt.param_groups):
             raise RuntimeError("CapturedTrainStep: needs a fused AdamW with capturable=True "
                                "(make_optimizer(..., capturable=True))")
-        if not all(t.is_cuda for t in batch):
-            raise RuntimeError("CapturedTrainStep: GPU batch tensors only (no CPU fallback)")
-        self.static = [t.detach().clone() for t in batch]
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps > 1:
+            if len(batch) != self.accum_steps:
+                raise ValueError(f"CapturedTrainStep: accum_steps={accum_steps} needs that many micro-batches "
+                                 f"(got {len(batch)})")
+            if not all(t.is_cuda for mb in batch for t in mb):
+                raise RuntimeError("CapturedTrainStep: GPU batch tensors only (no CPU fallback)")
+            self.micro = [[t.detach().clone() for t in mb] for mb in batch]
+            self.static = [t for mb in self.micro for t in mb]
+            step_fn, first = train_step_accum, self.micro
+        else:
+            if not all(t.is_cuda for t in batch):
+                raise RuntimeError("CapturedTrainStep: GPU batch tensors only (no CPU fallback)")
+            self.static = [t.detach().clone() for t in batch]
+            step_fn, first = train_step, self.static
         args = (silog, seg_weight, silog_weight)
         m = _unwrap(model)
         saved = getattr(m, "graph_text", None)
@@ -385,17 +773,19 @@ class CapturedTrainStep:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 for _ in range(max(1, warmup)):  # caches, allocator pools, the weight-refresh descriptor
-                    train_step(model, opt, self.static, *args)
+                    step_fn(model, opt, first, *args)
             torch.cuda.current_stream(dev).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.loss = train_step(model, opt, self.static, *args)
+                self.loss = step_fn(model, opt, first, *args)
         finally:
             if saved is not None:
                 m.graph_text = saved
 
     def __call__(self, batch=None):
         if batch is not None:
+            if self.accum_steps > 1:
+                batch = [t for mb in batch for t in mb]
             for s, t in zip(self.static, batch):
                 if s.shape != t.shape or s.dtype != t.dtype:
                     raise ValueError(f"CapturedTrainStep was captured for {tuple(s.shape)} {s.dtype}, "

@@ -30,6 +30,8 @@
  *   dclip_upsample_eval_seg/depth  validate()'s resize + argmax / confusion matrix / CE and depth
  *                              errors, train_denseclip.py:294-684, denseclip/utils.py:109-139,
  *                              utils/depth_metrics.py:12-88
+ *   dclip_adamw_prepare/update torch.optim.AdamW.step + clip_grad_norm_ + the 1/grad_accum_steps loss scaling,
+ *                              train_denseclip.py:1061, 1154-1155, 1314, 1356-1358
  *   dclip_im2col               conv1 (16x16, stride 16, no bias) models.py:407,546
  *   dclip_tokens_fwd/bwd       flatten/transpose + CLS + pos add, models.py:548-556
  *   dclip_pos_interp_fwd/bwd   interpolate_pos_encoding models.py:514-540
@@ -553,6 +555,67 @@ int dclip_bn_fwd(int dt, const void* x, int64_t rows, int C, int64_t ld, const f
 int dclip_bn_bwd(int dt, const void* dy, const void* x, int64_t rows, int C, int64_t ld, const float* w,
                  const float* b, const float* mean, const float* rstd, float* ws, void* dx, float* dw,
                  float* db, int relu, const float* gscale, void* stream);
+
+/* Multi-tensor AdamW step with global-norm clipping, gradient-accumulation scaling and a learning
+ * rate read from device memory (optim.hip; train.FusedAdamW).  torch.optim.AdamW (decoupled weight
+ * decay) + torch.nn.utils.clip_grad_norm_ + the non-finite check + dclip_weight_refresh, in two
+ * passes over HBM; no atomics, bitwise reproducible.  An additive part of ABI 7.
+ *
+ * Descriptor: n entries of DCLIP_ADAMW_DESC_WORDS int64, on the device (desc, read by the kernels)
+ * and, identical, on the host (desc_host, read by the entry points: launch geometry and checks):
+ *   [0] p  [1] exp_avg m  [2] exp_avg_sq v   (f32, contiguous, numel = rows * cols)
+ *   [3] plain 16-bit copy (rows, cols) or 0   [4] transposed 16-bit copy (cols, rows) or 0
+ *   [5] rows  [6] cols  [7] first tile  [8] column tiles ceil(cols / 64), or 0: walked as flat
+ *   chunks of 4096 elements (required to be non-zero with a transposed copy)
+ *   [9] hyper-parameter row  [10] the copies' dtype (DCLIP_BF16 / DCLIP_F16)  [11] unused
+ * Entry e covers tiles [first, first + (tiles of its walk)); `tiles` is their total.  Copies must
+ * be 16-byte aligned; p, g, m, v take 16-byte accesses when all four are 16-byte aligned.
+ * grads: n HOST pointers to the f32 gradients in entry order (NULL: the entry is skipped this step).
+ * They are passed to the kernels as launch arguments, DCLIP_ADAMW_CHUNK entries per launch, so no
+ * buffer of the caller's has to outlive the call.
+ *
+ * hp: n_rows device rows of DCLIP_ADAMW_HP_FLOATS f32, one per param group:
+ *   lr, 1 - beta1, 1 - beta2, eps, weight_decay, max_norm (<= 0: no clipping), inv_accum, unused
+ * (the complements of the betas: 1 - 0.999 keeps in fp32 the digits that 0.999 would lose).
+ * The global norm and clip coefficient take max_norm and inv_accum from row 0.
+ *
+ * state: DCLIP_ADAMW_STATE_HEAD + n_rows * DCLIP_ADAMW_STATE_ROW_FLOATS device f32 the optimizer
+ * owns (zeroed once; [3] persists):
+ *   [0] total_norm  [1] clip coefficient  [2] found_inf (0 / 1)  [3] step count: the steps APPLIED
+ *   [4] the count of the prepared step (prepare writes it, update commits it to [3]), then per row
+ *   lr, lr*wd, lr/(1 - beta1^t), 1/sqrt(1 - beta2^t), 1 - beta1, beta2, 1 - beta2, eps, c, 3 unused.
+ *
+ * dclip_adamw_prepare: with_norm launches the partial sums (per element the exact fp64 square of
+ * the fp32 gradient; per thread in element order, a fixed 64-lane butterfly, the 4 waves in order:
+ * ONE fp64 partial per tile in ws, dclip_adamw_ws_bytes(tiles) bytes — a function of `tiles`
+ * alone).  Always launches the one-workgroup fold: sum = the partials added in a fixed order (0
+ * without the norm pass);
+ *   found_inf  = 1 when sum is not finite or *found_inf (optional device f32) is non-zero
+ *   total_norm = sqrt(sum) * inv_accum
+ *   coef       = min(1, max_norm / (total_norm + 1e-6)) when max_norm > 0, else 1  (clip_grad_norm_)
+ *   t          = [3] + 1 unless found_inf, to [4];  the bias corrections in fp64, stored as f32
+ *                (preparing twice, or without an update, counts nothing)
+ *   c          = coef * inv_accum (per row)
+ * dclip_adamw_update: one workgroup per tile; writes NOTHING when found_inf is 1.  Otherwise tile
+ * 0's workgroup commits the step count ([3] = [4]; nothing else reads [3] in this launch) and, fp32
+ * per element in torch's AdamW order, the gradient never rewritten:
+ *   g' = g c
+ *   p  = p (1 - lr wd)                      [as p - (lr wd) p, one rounding]
+ *   m  = m + (1 - beta1)(g' - m)
+ *   v  = beta2 v + (1 - beta2) g'^2
+ *   p  = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ * and the copies are the cast of the new p, as dclip_weight_refresh writes them. */
+#define DCLIP_ADAMW_DESC_WORDS 12
+#define DCLIP_ADAMW_CHUNK 256
+#define DCLIP_ADAMW_HP_FLOATS 8
+#define DCLIP_ADAMW_STATE_HEAD 8
+#define DCLIP_ADAMW_STATE_ROW_FLOATS 12
+int64_t dclip_adamw_ws_bytes(int64_t tiles);
+int dclip_adamw_prepare(const int64_t* desc, const int64_t* desc_host, const void* const* grads, int n,
+                        int64_t tiles, const float* hp, int n_rows, const float* found_inf, float* state,
+                        void* ws, int with_norm, void* stream);
+int dclip_adamw_update(const int64_t* desc, const int64_t* desc_host, const void* const* grads, int n,
+                       int64_t tiles, float* state, void* stream);
 
 #ifdef __cplusplus
 }
