@@ -104,6 +104,11 @@ _SIGS = {
                                 _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_upsample_eval_depth": [_i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
                                   _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "dclip_ensemble_eval_ws_bytes": [_i32, _i32, _i32],
+    "dclip_ensemble_eval_seg": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
+                                _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "dclip_ensemble_eval_depth": [_i32, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
+                                  _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_conv3x3_wgrad": [_i32, _c_void_p, _i64, _i32, _c_void_p, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
                             _c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p],
     "dclip_set_option": [_i32, _i32],
@@ -123,6 +128,17 @@ _SIGS = {
     "dclip_adamw_update": [_c_void_p, _c_void_p, _c_void_p, _i32, _i64, _c_void_p, _c_void_p],
 }
 EXPORTED = sorted(list(_SIGS) + ["dclip_last_error", "dclip_abi_version"])
+ENSEMBLE_MAX_VIEWS = 16
+
+
+class View(ctypes.Structure):
+    """dclip_view (include/dclip.h): one low-res map of the ensemble and its flip flag"""
+    _fields_ = [("low", ctypes.c_void_p), ("h", ctypes.c_int), ("w", ctypes.c_int), ("flip", ctypes.c_int)]
+
+
+def view_table(views):
+    """A host array of dclip_view from (pointer, h, w, flip) tuples, for dclip_ensemble_eval_*"""
+    return (View * len(views))(*[View(p, int(h), int(w), int(f)) for p, h, w, f in views])
 
 _lib = None
 _lock = threading.Lock()
@@ -161,6 +177,7 @@ def load(path=None):
         lib.dclip_upsample_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_adamw_ws_bytes.restype = ctypes.c_int64
+        lib.dclip_ensemble_eval_ws_bytes.restype = ctypes.c_int64
         # kernel-variant knobs for A/B runs: DCLIP_OPTIONS="id=value,..." (DCLIP_OPT_* ids of dclip.h)
         for kv in filter(None, os.environ.get("DCLIP_OPTIONS", "").split(",")):
             k, v = kv.split("=")

@@ -529,6 +529,9 @@ class DenseCLIP(nn.Module):
         return {"seg": seg, "depth": depth}
 
     def aug_test(self, imgs, img_metas, rescale=True):
+        """The reference's literal rule (denseclip.py:1005-1041): the mean of the views' full-size outputs, one
+        image at a time; a flipped view is averaged un-mirrored, as there.  evaluate.predict_tta / validate(tta=...)
+        is the fused, batched path, which mirrors flipped views back."""
         segs, depths = [], []
         for img, meta in zip(imgs, img_metas):
             out = self.inference(img.unsqueeze(0), [meta], rescale)

@@ -19,15 +19,23 @@ DepthMetricsAggregator (utils/depth_metrics.py:122-163) instead averages the per
 compute_depth_errors, which weights a call with few valid pixels like one with many;
 `update(..., per_call=True)` returns the call's own sums (`metrics_from_sums` turns them into that
 call's figures) for callers who want that average.
+
+Multi-scale + flip test-time augmentation (the reference's test.py --aug-test) runs on the same
+footing: `forward_views` keeps the low-res maps of every view, and `predict_tta` /
+`Evaluator.update_views` / `validate(..., tta=dict(...))` hand them to one fused kernel per head
+(csrc/headensemble.hip) that averages the resized, mirrored-back views in registers.
 """
 import math
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import _torch_ops
 
 DEPTH_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+TTA_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)  # the reference's --aug-test ratios (test.py:93-96)
+AVERAGES = ("logits", "probs")
 _LAB_DTYPES = (torch.int64, torch.int32, torch.uint8)
 
 
@@ -63,6 +71,58 @@ def predict(model, img, size=None):
         seg, depth = low["seg"], low["depth"]
         return {"seg": upsample_argmax(seg, size) if seg is not None else None,
                 "depth": ops.upsample(depth, size) if depth is not None else None}
+
+
+def _probs(average):
+    """the `probs` flag of the ensemble ops from the averaging rule's name"""
+    if average not in AVERAGES:
+        raise ValueError(f"average={average!r}: 'logits' (the mean of the views' resized logits, the reference's "
+                         "aug_test) or 'probs' (the mean of their softmax, mmseg's rule)")
+    return average == "probs"
+
+
+def tta_views(img, scales=TTA_SCALES, flip=True):
+    """Yield (view_img, flipped) for every scale, each followed by its horizontal mirror when `flip`:
+    F.interpolate(bilinear, align_corners=False) of the normalised image `img` (B, 3, H, W) to
+    (int(H s + 0.5), int(W s + 0.5)); scale 1 passes `img` through untouched.  This is torch's resize
+    of the float image, not cv2's 8-bit resize of the decoded one, which mmcv's MultiScaleFlipAug
+    uses: parity with that is not pinned."""
+    H, W = _hw(img)
+    for s in scales:
+        size = (int(H * s + 0.5), int(W * s + 0.5))
+        view = img if size == (H, W) else F.interpolate(img, size=size, mode="bilinear", align_corners=False)
+        yield view, False
+        if flip:
+            yield view.flip(-1), True
+
+
+def forward_views(model, img, scales=TTA_SCALES, flip=True):
+    """`model.forward_lowres` on every view of `tta_views`, one view at a time under no_grad, keeping
+    only the low-res maps: (seg_views, depth_views, flips), a list per head (None for a model
+    without that head) and the views' flip flags."""
+    segs, depths, flips = [], [], []
+    with torch.no_grad():
+        for view, flipped in tta_views(img, scales, flip):
+            low = model.forward_lowres(view)
+            if low["seg"] is not None:
+                segs.append(low["seg"].detach().contiguous())
+            if low["depth"] is not None:
+                depths.append(low["depth"].detach().contiguous())
+            flips.append(int(flipped))
+    return segs or None, depths or None, flips
+
+
+def predict_tta(model, img, scales=TTA_SCALES, flip=True, average="logits", size=None):
+    """`predict` under multi-scale + flip test-time augmentation: {'seg': uint8 (B, H, W), 'depth':
+    fp32 (B, 1, H, W)} from the mean over the views of the resized, mirrored-back outputs
+    (csrc/headensemble.hip: no per-view full-size tensor).  `average`: 'logits' or 'probs' for the
+    class map (the depth is always the mean of the predictions)."""
+    probs = _probs(average)
+    H, W = _hw(img) if size is None else (int(size[0]), int(size[1]))
+    segs, depths, flips = forward_views(model, img, scales, flip)
+    E = _E()
+    return {"seg": E.ensemble_argmax(segs, flips, H, W, probs) if segs else None,
+            "depth": E.ensemble_depth(depths, flips, H, W) if depths else None}
 
 
 def metrics_from_sums(cm=None, ce_sums=None, depth_sums=None, lambd=0.5):
@@ -154,6 +214,50 @@ class Evaluator:
                 self.depth_sums += sums
         return own
 
+    def update_views(self, seg_views=None, depth_views=None, flips=(), seg_target=None, depth_target=None,
+                     depth_mask=None, average="logits", per_call=False):
+        """`update` on the ensemble of one batch's views (`forward_views`): lists of low-res maps
+        (B, K, h_v, w_v) / (B, 1, h_v, w_v) and the views' flip flags; the metrics are taken from the
+        mean over the views of the resized, mirrored-back outputs (`average`: 'logits' or 'probs'
+        for the class map and the CE).  Same contract as `update`: no host synchronisation, no new
+        tensor besides the workspace, added to the running state; per_call=True returns the call's
+        own sums."""
+        probs = _probs(average)
+        E = _E()
+        flips = [int(f) for f in flips]
+        own = None
+        if per_call:
+            own = {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
+                   "depth_sums": torch.zeros_like(self.depth_sums)}
+        if seg_views and seg_target is not None:
+            for v in seg_views:
+                _need_gpu(v, "seg_views")
+                if v.shape[1] != self.num_classes:
+                    raise ValueError(f"Evaluator: {v.shape[1]} classes, built for {self.num_classes}")
+            lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
+            if lab.dtype not in _LAB_DTYPES:
+                lab = lab.long()
+            cm, ce = (own["cm"], own["ce_sums"]) if per_call else (self.cm, self.ce_sums)
+            E.ensemble_seg_update([v.detach().contiguous() for v in seg_views], flips, lab.contiguous(),
+                                  self.ignore_index, probs, cm, ce, False)
+            if per_call:
+                self.cm += cm
+                self.ce_sums += ce
+        if depth_views and depth_target is not None:
+            for v in depth_views:
+                _need_gpu(v, "depth_views")
+            B = depth_target.shape[0]
+            tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
+            mk = None
+            if depth_mask is not None:
+                mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
+            sums = own["depth_sums"] if per_call else self.depth_sums
+            E.ensemble_depth_update([v.detach().contiguous() for v in depth_views], flips, tg, mk, self.min_depth,
+                                    self.max_depth, self.clamp_pred, self.eps, sums, False)
+            if per_call:
+                self.depth_sums += sums
+        return own
+
     def all_reduce(self, group=None):
         """Sum the state over the ranks of `group`: one all_reduce per state tensor."""
         import torch.distributed as dist
@@ -170,12 +274,21 @@ class Evaluator:
                                  self.lambd)
 
 
-def validate(model, batches, evaluator=None, **loss_cfg):
+def validate(model, batches, evaluator=None, tta=None, **loss_cfg):
     """Evaluate `model` over `batches` of (img, seg, depth, mask) (train.synth_batch's layout) in
     eval mode under no_grad, restore the model's mode, and return `evaluator.compute()`.  Under an
-    initialised process group the state is summed over the ranks first.  `loss_cfg`: Evaluator
-    keywords (lambd, eps, min_depth, ...) for the default evaluator."""
+    initialised process group the state is summed over the ranks first.  `tta`: None (one forward
+    per batch), or dict(scales=..., flip=..., average=...) (each optional: TTA_SCALES, True,
+    'logits') for multi-scale + flip test-time augmentation (`forward_views` + `update_views`).
+    `loss_cfg`: Evaluator keywords (lambd, eps, min_depth, ...) for the default evaluator."""
     import torch.distributed as dist
+    if tta is not None:
+        unknown = set(tta) - {"scales", "flip", "average"}
+        if unknown:
+            raise ValueError(f"validate: unknown tta keys {sorted(unknown)} (scales, flip, average)")
+        scales, flip = tta.get("scales", TTA_SCALES), tta.get("flip", True)
+        average = tta.get("average", "logits")
+        _probs(average)
     was_training = model.training
     model.eval()
     try:
@@ -183,6 +296,10 @@ def validate(model, batches, evaluator=None, **loss_cfg):
             for img, seg, depth, mask in batches:
                 if evaluator is None:
                     evaluator = Evaluator(device=img.device, **loss_cfg)
+                if tta is not None:
+                    segs, depths, flips = forward_views(model, img, scales, flip)
+                    evaluator.update_views(segs, depths, flips, seg, depth, mask, average=average)
+                    continue
                 low = model.forward_lowres(img)
                 evaluator.update(low["seg"], low["depth"], seg, depth, mask)
     finally:

@@ -406,6 +406,43 @@ int dclip_upsample_eval_depth(int low_dt, const void* pred, int B, int h, int w,
                               const uint8_t* mask, int H, int W, float min_depth, float max_depth, int clamp_pred,
                               float eps, float* up, double* sums, void* ws, void* stream);
 
+/* Multi-scale + flip test-time ensembling fused into the evaluation above (the reference's aug_test,
+ * denseclip.py:1005-1041 with test.py:91-96, without materialising one resized tensor per view).
+ * A view is a low-res map (B, K, h, w) of low_dt (one dtype, B and K for all views) and a flip flag;
+ * `views` is a HOST array of nviews (1 .. DCLIP_ENSEMBLE_MAX_VIEWS) entries, copied into the kernel
+ * arguments by the call (no device-side table, no copy: capturable).  Per output pixel (y, x), for
+ * every view in the order given, u_v = the bilinear resize (align_corners=False, the arithmetic of
+ * dclip_upsample_eval_*) of view v at (y, x_v), x_v = x for a plain view and W-1-x for a flipped one
+ * (the view's resized map mirrored back, F.interpolate(...).flip(-1)); the u_v are accumulated in f32
+ * in view order and scaled by 1/nviews.  h_v <= H, w_v <= W, B*H*W < 2^31.  Additive to ABI 7.
+ *   dclip_ensemble_eval_seg: K == 19.  average 0 ("logits", the reference's rule): the mean of the
+ *       u_v; CE = -log softmax(mean)[label].  average 1 ("probs", mmseg's rule): the mean of
+ *       softmax_K(u_v); CE = -log(mean[label]).  pred / labels / cm / loss_sum / count as
+ *       dclip_upsample_eval_seg, taken from the mean (argmax: the lowest index among equal maxima).
+ *   dclip_ensemble_eval_depth: views (B, 1, h, w).  up (nullable): f32 (B, H, W), the mean of the
+ *       resized, mirrored-back predictions; sums (f64[12]) += the sums of dclip_upsample_eval_depth
+ *       evaluated on that mean.  target null: prediction only (up required; mask, sums and ws unused).
+ * ws: dclip_ensemble_eval_ws_bytes(B, K, nviews) bytes (K = 1 for depth; a function of its arguments
+ * alone), 8-byte aligned, contents undefined on entry.  Reductions as dclip_upsample_eval_*: exact
+ * counts, f64 sums in a fixed order, two runs bitwise equal, no atomics on global memory.  The fused
+ * multiply-adds of the interpolation are spelled out so that a source column always goes through
+ * the same roundings: a flipped view gives exactly the column mirror of the same map unflipped.
+ * One plain view with average 0 gives the class map, confusion matrix and count of
+ * dclip_upsample_eval_seg and, bitwise, the up and sums of dclip_upsample_eval_depth (its CE sum
+ * is not bitwise dclip_upsample_eval_seg's: the resized logits may differ in their last bits).  */
+#define DCLIP_ENSEMBLE_MAX_VIEWS 16
+typedef struct {
+    const void* low;
+    int h, w, flip;
+} dclip_view;
+int64_t dclip_ensemble_eval_ws_bytes(int B, int K, int nviews);
+int dclip_ensemble_eval_seg(int low_dt, const dclip_view* views, int nviews, int B, int K, int average,
+                            const void* labels, int lab_dt, int H, int W, int ignore_index, uint8_t* pred,
+                            int64_t* cm, double* loss_sum, unsigned long long* count, void* ws, void* stream);
+int dclip_ensemble_eval_depth(int low_dt, const dclip_view* views, int nviews, int B, const float* target,
+                              const uint8_t* mask, int H, int W, float min_depth, float max_depth, int clamp_pred,
+                              float eps, float* up, double* sums, void* ws, void* stream);
+
 /* Cityscapes depth + segmentation batch preparation (datasets/cityscapes_depth_seg.py:129-170,
  * 218 and the trainer's RandomCrop / HorizontalFlip / Normalize / ToTensorV2,
  * train_denseclip.py:143-149).  Inputs: decoded planes of B images of H x W — img uint8
