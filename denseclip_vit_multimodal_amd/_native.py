@@ -109,6 +109,11 @@ _SIGS = {
                                 _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_ensemble_eval_depth": [_i32, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
                                   _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "dclip_slide_eval_ws_bytes": [_i32, _i32, _i32],
+    "dclip_slide_eval_seg": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32,
+                             _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "dclip_slide_eval_depth": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32,
+                               _f32, _f32, _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_conv3x3_wgrad": [_i32, _c_void_p, _i64, _i32, _c_void_p, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
                             _c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p],
     "dclip_set_option": [_i32, _i32],
@@ -139,6 +144,20 @@ class View(ctypes.Structure):
 def view_table(views):
     """A host array of dclip_view from (pointer, h, w, flip) tuples, for dclip_ensemble_eval_*"""
     return (View * len(views))(*[View(p, int(h), int(w), int(f)) for p, h, w, f in views])
+
+
+SLIDE_MAX_WINDOWS = 64
+
+
+class Window(ctypes.Structure):
+    """dclip_window (include/dclip.h): the low-res map of one sliding window and its origin in the image"""
+    _fields_ = [("low", ctypes.c_void_p), ("y0", ctypes.c_int), ("x0", ctypes.c_int)]
+
+
+def window_table(windows):
+    """A host array of dclip_window from (pointer, y0, x0) tuples, for dclip_slide_eval_*"""
+    return (Window * len(windows))(*[Window(p, int(y), int(x)) for p, y, x in windows])
+
 
 _lib = None
 _lock = threading.Lock()
@@ -178,6 +197,7 @@ def load(path=None):
         lib.dclip_upsample_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_adamw_ws_bytes.restype = ctypes.c_int64
         lib.dclip_ensemble_eval_ws_bytes.restype = ctypes.c_int64
+        lib.dclip_slide_eval_ws_bytes.restype = ctypes.c_int64
         # kernel-variant knobs for A/B runs: DCLIP_OPTIONS="id=value,..." (DCLIP_OPT_* ids of dclip.h)
         for kv in filter(None, os.environ.get("DCLIP_OPTIONS", "").split(",")):
             k, v = kv.split("=")

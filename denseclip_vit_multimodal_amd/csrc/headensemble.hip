@@ -80,39 +80,6 @@ __device__ __forceinline__ TileGeom view_geom(int b, int y0, int x0, int tw, con
     return g;
 }
 
-// One interpolated value, with every fused multiply-add spelled out.  headeval.hip leaves
-// Y.l0 * (X.l0 * a00 + X.l1 * a01) + Y.l1 * (...) to the compiler's contraction, and the compiler
-// does not fuse a thread's four pixels (slots) alike.  Here a flipped view must be the exact mirror
-// of the plain one, and a pixel and its mirror sit in different slots, so the roundings are fixed.
-//   bilerp:       the form of most of headeval's slots, for every slot (the segmentation kernel).
-//   bilerp_depth: the forms eval_depth_kernel compiles to on gfx950, per slot, read from its
-//                 assembly: slot 0 fuses the outer sum on the bottom row, slot 1 the top row's sum
-//                 on its right tap, everything else as bilerp.  With these, one plain view is
-//                 bitwise dclip_upsample_eval_depth (test_gpu_tta.py pins it; a compiler that fuses
-//                 headeval.hip otherwise shows up there).  The depth kernel keeps a source column
-//                 in the slot column % 4, flipped or not, so the mirror stays exact.
-__device__ __forceinline__ float bilerp(float yl0, float yl1, float xl0, float xl1, float a00, float a01, float a10,
-                                        float a11) {
-#pragma clang fp contract(off)
-    const float top = fmaf(xl0, a00, xl1 * a01);
-    const float bot = fmaf(xl0, a10, xl1 * a11);
-    return fmaf(yl0, top, yl1 * bot);
-}
-__device__ __forceinline__ float bilerp_depth(int slot, float yl0, float yl1, float xl0, float xl1, float a00,
-                                              float a01, float a10, float a11) {
-#pragma clang fp contract(off)
-    const float top = slot == 1 ? fmaf(xl1, a01, xl0 * a00) : fmaf(xl0, a00, xl1 * a01);
-    const float bot = fmaf(xl0, a10, xl1 * a11);
-    return slot == 0 ? fmaf(yl1, bot, yl0 * top) : fmaf(yl0, top, yl1 * bot);
-}
-
-// acc + u as one rounded add the compiler cannot fuse into the arithmetic that produced u: the
-// views are summed as f32 values, in view order
-__device__ __forceinline__ float add_rounded(float acc, float u) {
-#pragma clang fp contract(off)
-    return acc + u;
-}
-
 // ----------------------------------------------------------------------------- segmentation
 // LAB: labels given (confusion matrix, CE sum, #valid); pred may be null then.  !LAB: pred only.
 // PROBS: accumulate softmax(resized logits) of every view instead of the resized logits.

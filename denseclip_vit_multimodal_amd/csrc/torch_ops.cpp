@@ -1067,6 +1067,111 @@ c10::optional<Tensor> ensemble_depth_update(at::TensorList preds, at::IntArrayRe
     return up;
 }
 
+// ----------------------------------------------------------------------------- fused sliding-window inference
+// the host window table of dclip_slide_eval_* from the windows' low-res maps (B, K, h, w), all of one
+// shape, and their origins (y0, x0, y0, x0, ...)
+std::vector<dclip_window> slide_windows(at::TensorList maps, at::IntArrayRef origins, bool depth, const char* op) {
+    TORCH_CHECK(!maps.empty() && maps.size() <= DCLIP_SLIDE_MAX_WINDOWS, op, ": ", maps.size(), " windows (1 .. ",
+                DCLIP_SLIDE_MAX_WINDOWS, ")");
+    TORCH_CHECK(origins.size() == 2 * maps.size(), op, ": ", maps.size(), " windows but ", origins.size(),
+                " origin coordinates (y0, x0 per window)");
+    std::vector<dclip_window> wins;
+    const Tensor& first = maps[0];
+    for (size_t i = 0; i < maps.size(); ++i) {
+        const Tensor& t = maps[i];
+        check_gpu(t, "window");
+        TORCH_CHECK(t.dim() == 4 && (!depth || t.size(1) == 1), op, ": window ", i, " must be (B, ",
+                    depth ? "1" : "K", ", h, w)");
+        TORCH_CHECK(t.device() == first.device() && t.scalar_type() == first.scalar_type() &&
+                        t.sizes() == first.sizes(),
+                    op, ": window ", i, " differs from window 0 in device, dtype or shape");
+        wins.push_back(dclip_window{t.data_ptr(), (int)origins[2 * i], (int)origins[2 * i + 1]});
+    }
+    return wins;
+}
+
+Tensor slide_ws(const Tensor& low, int64_t K, size_t nwin) {
+    return at::empty({dclip_slide_eval_ws_bytes((int)low.size(0), (int)K, (int)nwin)}, like(low, at::kByte));
+}
+
+// argmax class map u8 (B, H, W) of the mean of the covering windows' logits resized to wh x ww
+Tensor slide_argmax(at::TensorList logits, at::IntArrayRef origins, int64_t wh, int64_t ww, int64_t H, int64_t W) {
+    const std::vector<dclip_window> wins = slide_windows(logits, origins, false, "slide_argmax");
+    const Tensor& l0 = logits[0];
+    c10::DeviceGuard g(l0.device());
+    Tensor pred = at::empty({l0.size(0), H, W}, like(l0, at::kByte));
+    DCLIP_CALL(dclip_slide_eval_seg(dt_code(l0.scalar_type()), wins.data(), (int)wins.size(), (int)l0.size(0),
+                                    (int)l0.size(1), (int)l0.size(2), (int)l0.size(3), (int)wh, (int)ww, nullptr, 0,
+                                    (int)H, (int)W, 0, ptr<uint8_t>(pred), nullptr, nullptr, nullptr, nullptr,
+                                    stream_of(l0)));
+    return pred;
+}
+
+// seg_update on the windows' mean
+c10::optional<Tensor> slide_seg_update(at::TensorList logits, at::IntArrayRef origins, int64_t wh, int64_t ww,
+                                       const Tensor& labels, int64_t ignore_index, Tensor& cm, Tensor& ce_sums,
+                                       bool want_pred) {
+    const std::vector<dclip_window> wins = slide_windows(logits, origins, false, "slide_seg_update");
+    const Tensor& l0 = logits[0];
+    check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
+    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == l0.size(0), "slide_seg_update: shapes");
+    const int64_t K = l0.size(1);
+    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, "slide_seg_update: cm must be int64 (K, K)");
+    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2,
+                "slide_seg_update: ce_sums must be float64[2]");
+    c10::DeviceGuard g(l0.device());
+    const int64_t H = labels.size(1), W = labels.size(2);
+    Tensor pred = want_pred ? at::empty({l0.size(0), H, W}, like(l0, at::kByte)) : Tensor();
+    Tensor cnt = at::zeros({1}, like(l0, at::kLong));
+    Tensor ws = slide_ws(l0, K, wins.size());
+    DCLIP_CALL(dclip_slide_eval_seg(dt_code(l0.scalar_type()), wins.data(), (int)wins.size(), (int)l0.size(0), (int)K,
+                                    (int)l0.size(2), (int)l0.size(3), (int)wh, (int)ww, labels.data_ptr(),
+                                    lab_code(labels.scalar_type()), (int)H, (int)W, (int)ignore_index,
+                                    ptr<uint8_t>(pred), ptr<int64_t>(cm), ptr<double>(ce_sums),
+                                    (unsigned long long*)cnt.data_ptr(), ws.data_ptr(), stream_of(l0)));
+    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
+    if (!want_pred) return c10::nullopt;
+    return pred;
+}
+
+// f32 (B, 1, H, W): the mean of the covering windows' depth predictions resized to wh x ww
+Tensor slide_depth(at::TensorList preds, at::IntArrayRef origins, int64_t wh, int64_t ww, int64_t H, int64_t W) {
+    const std::vector<dclip_window> wins = slide_windows(preds, origins, true, "slide_depth");
+    const Tensor& p0 = preds[0];
+    c10::DeviceGuard g(p0.device());
+    Tensor up = at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat));
+    DCLIP_CALL(dclip_slide_eval_depth(dt_code(p0.scalar_type()), wins.data(), (int)wins.size(), (int)p0.size(0),
+                                      (int)p0.size(2), (int)p0.size(3), (int)wh, (int)ww, nullptr, nullptr, (int)H,
+                                      (int)W, 0.f, 0.f, 0, 0.f, ptr<float>(up), nullptr, nullptr, stream_of(p0)));
+    return up;
+}
+
+// depth_update on the windows' mean
+c10::optional<Tensor> slide_depth_update(at::TensorList preds, at::IntArrayRef origins, int64_t wh, int64_t ww,
+                                         const Tensor& target, const c10::optional<Tensor>& mask, double min_depth,
+                                         double max_depth, bool clamp_pred, double eps, Tensor& sums, bool want_up) {
+    const std::vector<dclip_window> wins = slide_windows(preds, origins, true, "slide_depth_update");
+    const Tensor& p0 = preds[0];
+    check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
+    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == p0.size(0),
+                "slide_depth_update: target (B, H, W) fp32");
+    const bool has_mask = mask.has_value() && mask->defined();
+    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()),
+                "slide_depth_update: mask (B, H, W) uint8");
+    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12, "slide_depth_update: sums must be float64[12]");
+    c10::DeviceGuard g(p0.device());
+    const int64_t H = target.size(1), W = target.size(2);
+    Tensor up = want_up ? at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat)) : Tensor();
+    Tensor ws = slide_ws(p0, 1, wins.size());
+    DCLIP_CALL(dclip_slide_eval_depth(dt_code(p0.scalar_type()), wins.data(), (int)wins.size(), (int)p0.size(0),
+                                      (int)p0.size(2), (int)p0.size(3), (int)wh, (int)ww, ptr<float>(target),
+                                      optr<uint8_t>(mask), (int)H, (int)W, (float)min_depth, (float)max_depth,
+                                      clamp_pred ? 1 : 0, (float)eps, ptr<float>(up), ptr<double>(sums), ws.data_ptr(),
+                                      stream_of(p0)));
+    if (!want_up) return c10::nullopt;
+    return up;
+}
+
 // ----------------------------------------------------------------------------- optimizer
 // dclip_adamw_* (optim.hip): desc (n, 12) int64 on the GPU, desc_host the same table on the CPU,
 // grads the f32 gradients in entry order (an undefined / empty tensor: no gradient this step)
@@ -1254,6 +1359,13 @@ TORCH_LIBRARY(dclip_eval, m) {
     m.def("ensemble_depth(Tensor[] preds, int[] flips, int H, int W) -> Tensor");
     m.def("ensemble_depth_update(Tensor[] preds, int[] flips, Tensor target, Tensor? mask, float min_depth, "
           "float max_depth, bool clamp_pred, float eps, Tensor(a!) sums, bool want_up) -> Tensor?");
+    // the same on the mean of the sliding windows that cover a pixel (headslide.hip); origins = y0, x0, ...
+    m.def("slide_argmax(Tensor[] logits, int[] origins, int wh, int ww, int H, int W) -> Tensor");
+    m.def("slide_seg_update(Tensor[] logits, int[] origins, int wh, int ww, Tensor labels, int ignore_index, "
+          "Tensor(a!) cm, Tensor(b!) ce_sums, bool want_pred) -> Tensor?");
+    m.def("slide_depth(Tensor[] preds, int[] origins, int wh, int ww, int H, int W) -> Tensor");
+    m.def("slide_depth_update(Tensor[] preds, int[] origins, int wh, int ww, Tensor target, Tensor? mask, "
+          "float min_depth, float max_depth, bool clamp_pred, float eps, Tensor(a!) sums, bool want_up) -> Tensor?");
 }
 
 TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
@@ -1264,6 +1376,10 @@ TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
     m.impl("ensemble_seg_update", &ensemble_seg_update);
     m.impl("ensemble_depth", &ensemble_depth);
     m.impl("ensemble_depth_update", &ensemble_depth_update);
+    m.impl("slide_argmax", &slide_argmax);
+    m.impl("slide_seg_update", &slide_seg_update);
+    m.impl("slide_depth", &slide_depth);
+    m.impl("slide_depth_update", &slide_depth_update);
 }
 
 // The native optimizer step (optim.hip).  p, m, v and the 16-bit copies are written through the

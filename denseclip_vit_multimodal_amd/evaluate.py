@@ -24,6 +24,12 @@ Multi-scale + flip test-time augmentation (the reference's test.py --aug-test) r
 footing: `forward_views` keeps the low-res maps of every view, and `predict_tta` /
 `Evaluator.update_views` / `validate(..., tta=dict(...))` hand them to one fused kernel per head
 (csrc/headensemble.hip) that averages the resized, mirrored-back views in registers.
+
+Sliding-window inference (test_cfg mode='slide' of the reference's ViT configs, mmseg's
+slide_inference) likewise: `forward_windows` runs the model on the overlapping crops of
+`slide_windows` and keeps their low-res maps, and `predict_slide` / `Evaluator.update_windows` /
+`validate(..., slide=dict(crop_size=..., stride=...))` hand them to one fused kernel per head
+(csrc/headslide.hip) that averages, per pixel, the windows that cover it.
 """
 import math
 
@@ -32,6 +38,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _torch_ops
+from ._native import SLIDE_MAX_WINDOWS
 
 DEPTH_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 TTA_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)  # the reference's --aug-test ratios (test.py:93-96)
@@ -123,6 +130,90 @@ def predict_tta(model, img, scales=TTA_SCALES, flip=True, average="logits", size
     E = _E()
     return {"seg": E.ensemble_argmax(segs, flips, H, W, probs) if segs else None,
             "depth": E.ensemble_depth(depths, flips, H, W) if depths else None}
+
+
+def _pair(v, what):
+    """(a, b) of positive ints from an int or a pair"""
+    try:
+        a, b = (v, v) if isinstance(v, int) else v
+        a, b = int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError(f"slide: {what}={v!r}: a positive int or a pair of them") from None
+    if a <= 0 or b <= 0:
+        raise ValueError(f"slide: {what}={v!r} must be positive")
+    return a, b
+
+
+def slide_windows(H, W, crop_size, stride):
+    """The windows of mmseg's slide_inference on an H x W image: ((wh, ww), [(y0, x0), ...]), row by
+    row.  With crop_size (ch, cw) and stride (sh, sw) (ints or pairs) there are
+    max(H - ch + sh - 1, 0) // sh + 1 rows of windows (columns likewise); window (i, j) ends at
+    y2 = min(i sh + ch, H) and starts at max(y2 - ch, 0), so every window is min(ch, H) x min(cw, W)
+    and the last of a row or column is shifted back, not shrunk."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"slide: image size {H} x {W} must be positive")
+    (ch, cw), (sh, sw) = _pair(crop_size, "crop_size"), _pair(stride, "stride")
+    h_grids = max(H - ch + sh - 1, 0) // sh + 1
+    w_grids = max(W - cw + sw - 1, 0) // sw + 1
+    if h_grids * w_grids > SLIDE_MAX_WINDOWS:
+        raise ValueError(f"slide: {h_grids} x {w_grids} = {h_grids * w_grids} windows on a {H} x {W} image with "
+                         f"crop_size={(ch, cw)}, stride={(sh, sw)} (at most {SLIDE_MAX_WINDOWS})")
+    origins = []
+    for i in range(h_grids):
+        for j in range(w_grids):
+            y2, x2 = min(i * sh + ch, H), min(j * sw + cw, W)
+            origins.append((max(y2 - ch, 0), max(x2 - cw, 0)))
+    return (min(ch, H), min(cw, W)), origins
+
+
+def slide_from_test_cfg(test_cfg):
+    """validate's `slide` keywords from a model's test_cfg: dict(crop_size=..., stride=...) for
+    dict(mode='slide', crop_size=..., stride=...) (the reference's ViT configs), None for any other mode
+    ('whole', or no test_cfg)."""
+    if not isinstance(test_cfg, dict) or test_cfg.get("mode") != "slide":
+        return None
+    if "crop_size" not in test_cfg or "stride" not in test_cfg:
+        raise ValueError(f"test_cfg={test_cfg!r}: mode='slide' needs crop_size and stride")
+    return {"crop_size": test_cfg["crop_size"], "stride": test_cfg["stride"]}
+
+
+def forward_windows(model, img, crop_size, stride, windows_per_forward=None):
+    """`model.forward_lowres` on every window of `slide_windows` under no_grad, keeping only the
+    low-res maps: (seg_lows, depth_lows, (wh, ww), origins), a list of (B, K, h, w) / (B, 1, h, w)
+    maps per head (None for a model without that head) in the order of `origins`.  One window (all B
+    images) per forward by default; `windows_per_forward` = n runs n windows concatenated along the
+    batch."""
+    H, W = _hw(img)
+    (wh, ww), origins = slide_windows(H, W, crop_size, stride)
+    n = 1 if windows_per_forward is None else int(windows_per_forward)
+    if n <= 0:
+        raise ValueError(f"slide: windows_per_forward={windows_per_forward!r} must be positive")
+    B = img.shape[0]
+    segs, depths = [], []
+    with torch.no_grad():
+        for i in range(0, len(origins), n):
+            crops = [img[:, :, y0:y0 + wh, x0:x0 + ww] for y0, x0 in origins[i:i + n]]
+            low = model.forward_lowres(crops[0].contiguous() if len(crops) == 1 else torch.cat(crops, 0))
+            for head, out in ((low["seg"], segs), (low["depth"], depths)):
+                if head is not None:
+                    out.extend(c.contiguous() for c in head.detach().split(B, 0))
+    return segs or None, depths or None, (wh, ww), origins
+
+
+def _flat(origins):
+    return [int(c) for o in origins for c in o]
+
+
+def predict_slide(model, img, crop_size, stride, windows_per_forward=None):
+    """`predict` under sliding-window inference (mmseg's test_cfg mode='slide'): {'seg': uint8
+    (B, H, W), 'depth': fp32 (B, 1, H, W)} from the mean, over the windows that cover a pixel, of the
+    windows' outputs resized to the window size (csrc/headslide.hip: no image-sized accumulator)."""
+    H, W = _hw(img)
+    segs, depths, (wh, ww), origins = forward_windows(model, img, crop_size, stride, windows_per_forward)
+    E = _E()
+    return {"seg": E.slide_argmax(segs, _flat(origins), wh, ww, H, W) if segs else None,
+            "depth": E.slide_depth(depths, _flat(origins), wh, ww, H, W) if depths else None}
 
 
 def metrics_from_sums(cm=None, ce_sums=None, depth_sums=None, lambd=0.5):
@@ -258,6 +349,50 @@ class Evaluator:
                 self.depth_sums += sums
         return own
 
+    def update_windows(self, seg_lows=None, depth_lows=None, window_size=None, origins=(), seg_target=None,
+                       depth_target=None, depth_mask=None, per_call=False):
+        """`update` on one batch's sliding windows (`forward_windows`): lists of low-res maps
+        (B, K, h, w) / (B, 1, h, w), the windows' size (wh, ww) at the image's resolution and their
+        origins [(y0, x0), ...]; the metrics are taken from the mean, over the windows that cover a
+        pixel, of the windows' outputs resized to (wh, ww).  Same contract as `update`: no host
+        synchronisation, no new tensor besides the workspace, added to the running state;
+        per_call=True returns the call's own sums."""
+        E = _E()
+        wh, ww = int(window_size[0]), int(window_size[1])
+        flat = _flat(origins)
+        own = None
+        if per_call:
+            own = {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
+                   "depth_sums": torch.zeros_like(self.depth_sums)}
+        if seg_lows and seg_target is not None:
+            for v in seg_lows:
+                _need_gpu(v, "seg_lows")
+                if v.shape[1] != self.num_classes:
+                    raise ValueError(f"Evaluator: {v.shape[1]} classes, built for {self.num_classes}")
+            lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
+            if lab.dtype not in _LAB_DTYPES:
+                lab = lab.long()
+            cm, ce = (own["cm"], own["ce_sums"]) if per_call else (self.cm, self.ce_sums)
+            E.slide_seg_update([v.detach().contiguous() for v in seg_lows], flat, wh, ww, lab.contiguous(),
+                               self.ignore_index, cm, ce, False)
+            if per_call:
+                self.cm += cm
+                self.ce_sums += ce
+        if depth_lows and depth_target is not None:
+            for v in depth_lows:
+                _need_gpu(v, "depth_lows")
+            B = depth_target.shape[0]
+            tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
+            mk = None
+            if depth_mask is not None:
+                mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
+            sums = own["depth_sums"] if per_call else self.depth_sums
+            E.slide_depth_update([v.detach().contiguous() for v in depth_lows], flat, wh, ww, tg, mk, self.min_depth,
+                                 self.max_depth, self.clamp_pred, self.eps, sums, False)
+            if per_call:
+                self.depth_sums += sums
+        return own
+
     def all_reduce(self, group=None):
         """Sum the state over the ranks of `group`: one all_reduce per state tensor."""
         import torch.distributed as dist
@@ -274,13 +409,17 @@ class Evaluator:
                                  self.lambd)
 
 
-def validate(model, batches, evaluator=None, tta=None, **loss_cfg):
+def validate(model, batches, evaluator=None, tta=None, slide=None, **loss_cfg):
     """Evaluate `model` over `batches` of (img, seg, depth, mask) (train.synth_batch's layout) in
     eval mode under no_grad, restore the model's mode, and return `evaluator.compute()`.  Under an
     initialised process group the state is summed over the ranks first.  `tta`: None (one forward
     per batch), or dict(scales=..., flip=..., average=...) (each optional: TTA_SCALES, True,
     'logits') for multi-scale + flip test-time augmentation (`forward_views` + `update_views`).
-    `loss_cfg`: Evaluator keywords (lambd, eps, min_depth, ...) for the default evaluator."""
+    `slide`: None, dict(crop_size=..., stride=...[, windows_per_forward=...]) for sliding-window
+    inference (`forward_windows` + `update_windows`), or True to take crop_size and stride from
+    `model.test_cfg` (which must then be dict(mode='slide', crop_size=..., stride=...)); `slide` and
+    `tta` do not combine.  `loss_cfg`: Evaluator keywords (lambd, eps, min_depth, ...) for the default
+    evaluator."""
     import torch.distributed as dist
     if tta is not None:
         unknown = set(tta) - {"scales", "flip", "average"}
@@ -289,6 +428,24 @@ def validate(model, batches, evaluator=None, tta=None, **loss_cfg):
         scales, flip = tta.get("scales", TTA_SCALES), tta.get("flip", True)
         average = tta.get("average", "logits")
         _probs(average)
+    if slide is not None and slide is not False:
+        if tta is not None:
+            raise ValueError("validate: slide and tta do not combine (sliding windows over multi-scale + flip views "
+                             "are not implemented)")
+        if slide is True:
+            slide = slide_from_test_cfg(getattr(model, "test_cfg", None))
+            if slide is None:
+                raise ValueError(f"validate: slide=True needs model.test_cfg = dict(mode='slide', crop_size=..., "
+                                 f"stride=...), got {getattr(model, 'test_cfg', None)!r}")
+        unknown = set(slide) - {"crop_size", "stride", "windows_per_forward"}
+        if unknown:
+            raise ValueError(f"validate: unknown slide keys {sorted(unknown)} (crop_size, stride, "
+                             "windows_per_forward)")
+        if "crop_size" not in slide or "stride" not in slide:
+            raise ValueError("validate: slide needs crop_size and stride")
+        _pair(slide["crop_size"], "crop_size"), _pair(slide["stride"], "stride")
+    else:
+        slide = None
     was_training = model.training
     model.eval()
     try:
@@ -299,6 +456,10 @@ def validate(model, batches, evaluator=None, tta=None, **loss_cfg):
                 if tta is not None:
                     segs, depths, flips = forward_views(model, img, scales, flip)
                     evaluator.update_views(segs, depths, flips, seg, depth, mask, average=average)
+                    continue
+                if slide is not None:
+                    segs, depths, size, origins = forward_windows(model, img, **slide)
+                    evaluator.update_windows(segs, depths, size, origins, seg, depth, mask)
                     continue
                 low = model.forward_lowres(img)
                 evaluator.update(low["seg"], low["depth"], seg, depth, mask)

@@ -30,6 +30,8 @@
  *   dclip_upsample_eval_seg/depth  validate()'s resize + argmax / confusion matrix / CE and depth
  *                              errors, train_denseclip.py:294-684, denseclip/utils.py:109-139,
  *                              utils/depth_metrics.py:12-88
+ *   dclip_slide_eval_seg/depth test_cfg mode='slide' of configs/denseclip_fpn_vit-b_640x640_80k.py:51 (the
+ *                              rule is mmseg's slide_inference, restated at the entry points)
  *   dclip_adamw_prepare/update torch.optim.AdamW.step + clip_grad_norm_ + the 1/grad_accum_steps loss scaling,
  *                              train_denseclip.py:1061, 1154-1155, 1314, 1356-1358
  *   dclip_im2col               conv1 (16x16, stride 16, no bias) models.py:407,546
@@ -442,6 +444,51 @@ int dclip_ensemble_eval_seg(int low_dt, const dclip_view* views, int nviews, int
 int dclip_ensemble_eval_depth(int low_dt, const dclip_view* views, int nviews, int B, const float* target,
                               const uint8_t* mask, int H, int W, float min_depth, float max_depth, int clamp_pred,
                               float eps, float* up, double* sums, void* ws, void* stream);
+
+/* Sliding-window inference fused into the evaluation above (test_cfg mode='slide' of the reference's
+ * ViT configs; the rule is mmseg's slide_inference, which the reference tree only names), without
+ * the image-sized (B, K, H, W) accumulator and count map.  The caller runs the model on crops
+ * img[:, :, y0:y0+wh, x0:x0+ww] of one size wh x ww; a window is the crop's low-res map (B, K, h, w)
+ * of low_dt (one dtype, B, K, h and w for all windows) and its origin (y0, x0) in the H x W image.
+ * mmseg places them, for crop_size (ch, cw) and stride (sh, sw), at
+ *     h_grids = max(H - ch + sh - 1, 0) / sh + 1        (w_grids likewise)
+ *     window (i, j), i-major:  y2 = min(i sh + ch, H), y0 = max(y2 - ch, 0)   (x0 likewise)
+ * so wh x ww = min(ch, H) x min(cw, W) and the last window of a row or column is shifted back, not
+ * shrunk; any table that covers every pixel is accepted.  `wins` is a HOST array of nwin
+ * (1 .. DCLIP_SLIDE_MAX_WINDOWS) entries, copied into the kernel arguments by the call (no
+ * device-side table, no copy: capturable).  Per output pixel (y, x), for every window that covers it,
+ * in the order given, u = the bilinear resize (align_corners=False, the arithmetic of
+ * dclip_ensemble_eval_*) of the window's map to wh x ww at (y - y0, x - x0); the u are accumulated in
+ * f32 in table order and the result is sum / count, one correctly rounded division: a pixel that one
+ * window covers holds exactly that window's resized value.
+ * h <= wh <= H, w <= ww <= W, 0 <= y0 <= H - wh, 0 <= x0 <= W - ww, B*H*W < 2^31, and every pixel
+ * covered by at least one window (checked on the host; the message names the first uncovered pixel).
+ * Additive to ABI 7.
+ *   dclip_slide_eval_seg: K == 19.  CE = -log softmax(result)[label].  pred / labels / cm / loss_sum /
+ *       count as dclip_upsample_eval_seg, taken from the result (argmax: the lowest index among equal
+ *       maxima).  Without labels cm, loss_sum and count must be null (pred only; ws unused).
+ *   dclip_slide_eval_depth: windows (B, 1, h, w).  up (nullable): f32 (B, H, W), the mean of the
+ *       covering windows' resized predictions; sums (f64[12]) += the sums of
+ *       dclip_upsample_eval_depth evaluated on that mean.  target null: prediction only (up required;
+ *       mask, sums and ws unused).
+ * ws: dclip_slide_eval_ws_bytes(B, K, nwin) bytes (K = 1 for depth; a function of its arguments
+ * alone), 8-byte aligned, contents undefined on entry.  Reductions as dclip_upsample_eval_*: exact
+ * counts, f64 sums in a fixed order, two runs bitwise equal, no atomics on global memory.  One window
+ * covering the image gives, bitwise, what dclip_ensemble_eval_* gives for one plain view of the same
+ * map; a window's depth values are those of dclip_upsample_eval_depth on its map at the window's
+ * size, wherever the window lies (the roundings follow the window-local column).  */
+#define DCLIP_SLIDE_MAX_WINDOWS 64
+typedef struct {
+    const void* low;
+    int y0, x0;
+} dclip_window;
+int64_t dclip_slide_eval_ws_bytes(int B, int K, int nwin);
+int dclip_slide_eval_seg(int low_dt, const dclip_window* wins, int nwin, int B, int K, int h, int w, int wh, int ww,
+                         const void* labels, int lab_dt, int H, int W, int ignore_index, uint8_t* pred, int64_t* cm,
+                         double* loss_sum, unsigned long long* count, void* ws, void* stream);
+int dclip_slide_eval_depth(int low_dt, const dclip_window* wins, int nwin, int B, int h, int w, int wh, int ww,
+                           const float* target, const uint8_t* mask, int H, int W, float min_depth, float max_depth,
+                           int clamp_pred, float eps, float* up, double* sums, void* ws, void* stream);
 
 /* Cityscapes depth + segmentation batch preparation (datasets/cityscapes_depth_seg.py:129-170,
  * 218 and the trainer's RandomCrop / HorizontalFlip / Normalize / ToTensorV2,
