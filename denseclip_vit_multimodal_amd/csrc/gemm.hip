@@ -2715,8 +2715,10 @@ extern "C" int dclip_gemm_tn(int epilogue, int ab_dt, const void* A, int64_t lda
     const int tn_opt = dclip_option(DCLIP_OPT_GEMM_TN_TILE);
     const bool tn_pf = dclip_option(DCLIP_OPT_GEMM_KLOOP) == 1;
     const bool big = tn_opt != 1 && M >= 256 && N >= 256;
-    // the big kernel sums A's columns itself (DCLIP_OPT_GEMM_TN_COLSUM 1: the separate pass)
-    const bool fused_cs = colsum_a && big && dclip_option(DCLIP_OPT_GEMM_TN_COLSUM) != 1;
+    // the big kernel sums A's columns itself (DCLIP_OPT_GEMM_TN_COLSUM 1: the separate pass); its
+    // 32-row K-step variants (DCLIP_OPT_GEMM_TN_TILE 2, 3) have no fused sums: the separate pass as well
+    const bool fused_cs =
+        colsum_a && big && tn_opt != 2 && tn_opt != 3 && dclip_option(DCLIP_OPT_GEMM_TN_COLSUM) != 1;
     // the separate column-sum pass: per-split partials into ws's column-sum region (summed in
     // split order by the combine), or, for STORE (splits == 1), one block row over all K
     float* cs_sep = (colsum_a && !fused_cs && epilogue == DCLIP_EPI_SPLITK) ? (float*)ws + (int64_t)splits * M * N

@@ -176,9 +176,11 @@ int dclip_gemm(int epilogue, int ab_dt,
  * epilogue STORE (f32 C, splits == 1) or SPLITK (f32 slabs in ws, then a combine that adds
  * bias[n] when non-null; ws holds splits*(M*N + M) floats: the slabs, then (ABI 5) the column
  * sums' per-split partials).  colsum_a (f32, M), when non-null, receives += alpha * the column
- * sums of A over the K rows (the bias gradient of dY) — in a fixed order (deterministic) on the
- * 256x256 path (M, N >= 256), by per-row-chunk atomics on the small-tile path.  alpha_ptr as in
- * dclip_gemm.                                                                          */
+ * sums of A over the K rows (the bias gradient of dY) — in a fixed order on every path, so the
+ * result repeats bit for bit: inside the 256x256 kernel (M, N >= 256), or by a separate pass
+ * over A on the small-tile path and for the tiles without fused sums (one block row per split,
+ * each reducing its rows in LDS in a fixed order; no float atomics); with SPLITK the per-split
+ * partials are added in split order by the combine.  alpha_ptr as in dclip_gemm.        */
 /* The K-split plan dclip_gemm_tn runs best with for an M x N output over K rows
  * (splits, and K_pad = K rounded up to 64*splits); host-side only, no GPU work.      */
 int dclip_gemm_tn_plan(int64_t M, int64_t N, int64_t K, int* splits, int64_t* K_pad);

@@ -320,7 +320,13 @@ def test_gemm_tn_splitk_poisoned(dt, K, M, N, tile, forced, under):
     """C = A^T B through the split-K slabs of a poisoned workspace; K is not a multiple of 64, so
     K_pad > K and the rows >= K that "contribute zero" lie in the NaN band behind A and B.  splits
     from dclip_gemm_tn_plan, and forced to 3 with its K_pad (K = 70: the last split holds no row
-    at all).  colsum_a only where it is summed in a fixed order (the 256x256 kernel)."""
+    at all).  colsum_a is given here on the 256x256 kernel only, from the time the small-tile path
+    was thought to add it with atomics; it does not: colsum_kernel reduces each split's rows in LDS in
+    a fixed order and the combine adds the per-split partials in split order, so colsum_a repeats
+    bit for bit on every path (include/dclip.h says so now).  The small-tile path, and the 256x256
+    tiles without fused sums (DCLIP_OPT_GEMM_TN_TILE 2, 3), are held to an fp64 reference and to
+    bitwise equality between the two poison runs by test_gpu_conv_contract.py's
+    test_gemm_tn_splitk_strided."""
     import ctypes
     L = NT()
     torch.manual_seed(5)
