@@ -114,6 +114,11 @@ _SIGS = {
                              _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_slide_eval_depth": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32,
                                _f32, _f32, _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "dclip_slide_tta_eval_ws_bytes": [_i32, _i32, _i32, _i32],
+    "dclip_slide_tta_eval_seg": [_i32, _c_void_p, _i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32,
+                                 _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "dclip_slide_tta_eval_depth": [_i32, _c_void_p, _i32, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32,
+                                   _f32, _f32, _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_conv3x3_wgrad": [_i32, _c_void_p, _i64, _i32, _c_void_p, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
                             _c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p],
     "dclip_set_option": [_i32, _i32],
@@ -159,6 +164,21 @@ def window_table(windows):
     return (Window * len(windows))(*[Window(p, int(y), int(x)) for p, y, x in windows])
 
 
+SLIDE_TTA_MAX_WINDOWS = 1024
+
+
+class SlideView(ctypes.Structure):
+    """dclip_slide_view (include/dclip.h): one view of the ensemble, its window geometry and its
+    slice wins[first .. first + nwin) of the window table"""
+    _fields_ = [(n, ctypes.c_int) for n in ("Hv", "Wv", "flip", "wh", "ww", "h", "w", "first", "nwin")]
+
+
+def slide_view_table(views):
+    """A host array of dclip_slide_view from (Hv, Wv, flip, wh, ww, h, w, first, nwin) tuples, for
+    dclip_slide_tta_eval_* (the windows themselves go through `window_table`, origins in the view)"""
+    return (SlideView * len(views))(*[SlideView(*[int(c) for c in v]) for v in views])
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -198,6 +218,7 @@ def load(path=None):
         lib.dclip_adamw_ws_bytes.restype = ctypes.c_int64
         lib.dclip_ensemble_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_slide_eval_ws_bytes.restype = ctypes.c_int64
+        lib.dclip_slide_tta_eval_ws_bytes.restype = ctypes.c_int64
         # kernel-variant knobs for A/B runs: DCLIP_OPTIONS="id=value,..." (DCLIP_OPT_* ids of dclip.h)
         for kv in filter(None, os.environ.get("DCLIP_OPTIONS", "").split(",")):
             k, v = kv.split("=")

@@ -290,6 +290,24 @@ def _register_fakes():
         B, H, W = target.shape
         return _e(B, 1, H, W, like=preds[0], dtype=f32) if want_up else None
 
+    # the same on the mean over the views of their sliding-window results (csrc/headslidetta.hip)
+    @reg("dclip_eval::slide_tta_argmax")
+    def _(logits, views, origins, H, W, probs):
+        return _e(logits[0].shape[0], H, W, like=logits[0], dtype=torch.uint8)
+
+    @reg("dclip_eval::slide_tta_seg_update")
+    def _(logits, views, origins, labels, ignore_index, probs, cm, ce_sums, want_pred):
+        return _e(*labels.shape, like=logits[0], dtype=torch.uint8) if want_pred else None
+
+    @reg("dclip_eval::slide_tta_depth")
+    def _(preds, views, origins, H, W):
+        return _e(preds[0].shape[0], 1, H, W, like=preds[0], dtype=f32)
+
+    @reg("dclip_eval::slide_tta_depth_update")
+    def _(preds, views, origins, target, mask, min_depth, max_depth, clamp_pred, eps, sums, want_up):
+        B, H, W = target.shape
+        return _e(B, 1, H, W, like=preds[0], dtype=f32) if want_up else None
+
     # dclip_optim::* — the native AdamW step (csrc/optim.hip), a namespace of its own
     @reg("dclip_optim::adamw_prepare")
     def _(desc, desc_host, grads, tiles, hp, found_inf, state, with_norm):

@@ -1,10 +1,15 @@
 // The tile machinery shared by the fused head evaluation kernels (headeval.hip: one low-res map per
-// output pixel; headensemble.hip: V of them; headslide.hip: the windows that cover it): the resize's
+// output pixel; headensemble.hip: V of them; headslide.hip: the windows that cover it;
+// headslidetta.hip: the windows of V views): the resize's
 // source index, the low-res patch of an 8 x TW output tile and its LDS staging, the interpolation
-// with its fused multiply-adds spelled out (the ensemble's and the sliding windows'), the 4-pixel
+// with its fused multiply-adds spelled out (the ensemble's and the sliding windows'), the windows'
+// rounded division and host-side coverage check, the 4-pixel
 // label load, the per-workgroup record in the caller's workspace and the one-workgroup folds.
 // Everything here has internal linkage: each translation unit that includes it compiles its own copy.
 #pragma once
+#include <algorithm>
+#include <vector>
+
 #include "common.h"
 
 namespace {
@@ -111,6 +116,47 @@ __device__ __forceinline__ float bilerp_depth(int slot, float yl0, float yl1, fl
 __device__ __forceinline__ float add_rounded(float acc, float u) {
 #pragma clang fp contract(off)
     return acc + u;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// sum / count as one correctly rounded division the compiler cannot turn into a multiplication by
+// a reciprocal: a pixel covered once is exactly that window's resized value
+__device__ __forceinline__ float div_rounded(float acc, float cnt) {
+#pragma clang fp contract(off)
+    return acc / cnt;
+}
+
+// The first pixel (raster order) of an H x W image (or view) that none of the wh x ww windows covers,
+// by coordinate compression over the windows' edges: within a cell of the compressed grid every pixel
+// has the same set of windows, so the cell's top-left pixel decides.  False when every pixel is covered.
+inline bool first_uncovered(const dclip_window* wins, int nwin, int wh, int ww, int H, int W, int* py, int* px) {
+    std::vector<int> ys{0}, xs{0};
+    for (int i = 0; i < nwin; ++i) {
+        ys.push_back(wins[i].y0);
+        ys.push_back(wins[i].y0 + wh);
+        xs.push_back(wins[i].x0);
+        xs.push_back(wins[i].x0 + ww);
+    }
+    std::sort(ys.begin(), ys.end());
+    ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
+    std::sort(xs.begin(), xs.end());
+    xs.erase(std::unique(xs.begin(), xs.end()), xs.end());
+    for (int y : ys) {
+        if (y >= H) break;
+        for (int x : xs) {
+            if (x >= W) break;
+            bool hit = false;
+            for (int i = 0; i < nwin && !hit; ++i)
+                hit = y >= wins[i].y0 && y < wins[i].y0 + wh && x >= wins[i].x0 && x < wins[i].x0 + ww;
+            if (!hit) {
+                *py = y;
+                *px = x;
+                return true;
+            }
+        }
+    }
+    return false;
 }
 
 // 4 consecutive labels of one row; `vec`: the row segment is aligned for one vector load

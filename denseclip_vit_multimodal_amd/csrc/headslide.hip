@@ -49,8 +49,6 @@ Tiling make_tiling(int B, int K, const WinShape& s) {
     return t;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 // The patch of the window at (wy, wx) under the output tile at (y0, x0): tile_geom on the rows and
 // columns of the tile that lie inside the window, in window-local coordinates.  False when the tile
 // and the window do not intersect (a function of the tile alone: workgroup-uniform).
@@ -70,13 +68,6 @@ __device__ __forceinline__ bool win_geom(int y0, int x0, int tw, int wy, int wx,
     g.nr = g.nr < nrow ? g.nr : nrow;  // low_span() bounds both; never index LDS past the patch
     g.nc = g.nc < ncol ? g.nc : ncol;
     return true;
-}
-
-// sum / count as one correctly rounded division the compiler cannot turn into a multiplication by
-// a reciprocal: a pixel covered once is exactly that window's resized value
-__device__ __forceinline__ float div_rounded(float acc, float cnt) {
-#pragma clang fp contract(off)
-    return acc / cnt;
 }
 
 // ----------------------------------------------------------------------------- segmentation
@@ -393,42 +384,6 @@ void launch_depth(const WinTable& wt, const WinShape& s, int B, const float* gt,
         slide_depth_kernel<TL, false><<<tl.nwg, nth, tl.lds, st>>>(wt, s, tl, nullptr, nullptr, dmin, dmax, clamp_pred,
                                                                    eps, vec, up, nullptr);
     }
-}
-
-// The first pixel (raster order) that no window covers, by coordinate compression over the windows'
-// edges: within a cell of the compressed grid every pixel has the same set of windows, so the cell's
-// top-left pixel decides.  At most (2 MAXW + 1)^2 cells.  False when every pixel is covered.
-bool first_uncovered(const dclip_window* wins, int nwin, int wh, int ww, int H, int W, int* py, int* px) {
-    int ys[2 * MAXW + 2], xs[2 * MAXW + 2];
-    int ny = 0, nx = 0;
-    auto insert = [](int* a, int& n, int v) {
-        int i = 0;
-        while (i < n && a[i] < v) ++i;
-        if (i < n && a[i] == v) return;
-        for (int j = n; j > i; --j) a[j] = a[j - 1];
-        a[i] = v;
-        ++n;
-    };
-    insert(ys, ny, 0);
-    insert(xs, nx, 0);
-    for (int i = 0; i < nwin; ++i) {
-        insert(ys, ny, wins[i].y0);
-        insert(ys, ny, wins[i].y0 + wh);
-        insert(xs, nx, wins[i].x0);
-        insert(xs, nx, wins[i].x0 + ww);
-    }
-    for (int a = 0; a < ny && ys[a] < H; ++a)
-        for (int c = 0; c < nx && xs[c] < W; ++c) {
-            bool hit = false;
-            for (int i = 0; i < nwin && !hit; ++i)
-                hit = ys[a] >= wins[i].y0 && ys[a] < wins[i].y0 + wh && xs[c] >= wins[i].x0 && xs[c] < wins[i].x0 + ww;
-            if (!hit) {
-                *py = ys[a];
-                *px = xs[c];
-                return true;
-            }
-        }
-    return false;
 }
 
 }  // namespace

@@ -1172,6 +1172,138 @@ c10::optional<Tensor> slide_depth_update(at::TensorList preds, at::IntArrayRef o
     return up;
 }
 
+// ----------------------------------------------------------------------------- fused sliding windows under TTA
+// The host tables of dclip_slide_tta_eval_* from the windows' low-res maps (all views' windows, in
+// view order), views = (Hv, Wv, flip, wh, ww, nwin) per view and origins = (y0, x0) per window in
+// its view's coordinates.  The maps of one view have one shape; h and w are read from them.
+struct SlideTtaTables {
+    std::vector<dclip_slide_view> views;
+    std::vector<dclip_window> wins;
+};
+SlideTtaTables slide_tta_tables(at::TensorList maps, at::IntArrayRef views, at::IntArrayRef origins, bool depth,
+                                const char* op) {
+    TORCH_CHECK(!maps.empty() && maps.size() <= DCLIP_SLIDE_TTA_MAX_WINDOWS, op, ": ", maps.size(), " windows (1 .. ",
+                DCLIP_SLIDE_TTA_MAX_WINDOWS, ")");
+    TORCH_CHECK(!views.empty() && views.size() % 6 == 0 && views.size() / 6 <= DCLIP_ENSEMBLE_MAX_VIEWS, op, ": ",
+                views.size(), " view entries (Hv, Wv, flip, wh, ww, nwin per view, 1 .. ", DCLIP_ENSEMBLE_MAX_VIEWS,
+                " views)");
+    TORCH_CHECK(origins.size() == 2 * maps.size(), op, ": ", maps.size(), " windows but ", origins.size(),
+                " origin coordinates (y0, x0 per window)");
+    SlideTtaTables t;
+    const Tensor& first = maps[0];
+    size_t next = 0;
+    for (size_t v = 0; v < views.size() / 6; ++v) {
+        const int64_t* e = views.data() + 6 * v;
+        TORCH_CHECK(e[5] >= 1 && next + (size_t)e[5] <= maps.size(), op, ": view ", v, " has ", e[5],
+                    " windows, the list holds ", maps.size(), " in all");
+        const Tensor& m0 = maps[next];
+        for (size_t i = next; i < next + (size_t)e[5]; ++i) {
+            const Tensor& m = maps[i];
+            check_gpu(m, "window");
+            TORCH_CHECK(m.dim() == 4 && (!depth || m.size(1) == 1), op, ": window ", i, " must be (B, ",
+                        depth ? "1" : "K", ", h, w)");
+            TORCH_CHECK(m.device() == first.device() && m.scalar_type() == first.scalar_type() &&
+                            m.size(0) == first.size(0) && m.size(1) == first.size(1) && m.sizes() == m0.sizes(),
+                        op, ": window ", i, " differs from window 0 in device, dtype, batch or channels, or from the "
+                        "first window of its view in shape");
+            t.wins.push_back(dclip_window{m.data_ptr(), (int)origins[2 * i], (int)origins[2 * i + 1]});
+        }
+        t.views.push_back(dclip_slide_view{(int)e[0], (int)e[1], (int)e[2], (int)e[3], (int)e[4], (int)m0.size(2),
+                                           (int)m0.size(3), (int)next, (int)e[5]});
+        next += (size_t)e[5];
+    }
+    TORCH_CHECK(next == maps.size(), op, ": the views name ", next, " windows, the list holds ", maps.size());
+    return t;
+}
+
+Tensor slide_tta_ws(const Tensor& low, int64_t K, const SlideTtaTables& t) {
+    return at::empty({dclip_slide_tta_eval_ws_bytes((int)low.size(0), (int)K, (int)t.views.size(), (int)t.wins.size())},
+                     like(low, at::kByte));
+}
+
+// argmax class map u8 (B, H, W) of the mean over the views of their slide results resized to H x W
+Tensor slide_tta_argmax(at::TensorList logits, at::IntArrayRef views, at::IntArrayRef origins, int64_t H, int64_t W,
+                        bool probs) {
+    const SlideTtaTables t = slide_tta_tables(logits, views, origins, false, "slide_tta_argmax");
+    const Tensor& l0 = logits[0];
+    c10::DeviceGuard g(l0.device());
+    Tensor pred = at::empty({l0.size(0), H, W}, like(l0, at::kByte));
+    Tensor ws = slide_tta_ws(l0, l0.size(1), t);
+    DCLIP_CALL(dclip_slide_tta_eval_seg(dt_code(l0.scalar_type()), t.views.data(), (int)t.views.size(), t.wins.data(),
+                                        (int)t.wins.size(), (int)l0.size(0), (int)l0.size(1), probs ? 1 : 0, nullptr, 0,
+                                        (int)H, (int)W, 0, ptr<uint8_t>(pred), nullptr, nullptr, nullptr,
+                                        ws.data_ptr(), stream_of(l0)));
+    return pred;
+}
+
+// seg_update on that mean
+c10::optional<Tensor> slide_tta_seg_update(at::TensorList logits, at::IntArrayRef views, at::IntArrayRef origins,
+                                           const Tensor& labels, int64_t ignore_index, bool probs, Tensor& cm,
+                                           Tensor& ce_sums, bool want_pred) {
+    const SlideTtaTables t = slide_tta_tables(logits, views, origins, false, "slide_tta_seg_update");
+    const Tensor& l0 = logits[0];
+    check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
+    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == l0.size(0), "slide_tta_seg_update: shapes");
+    const int64_t K = l0.size(1);
+    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, "slide_tta_seg_update: cm must be int64 (K, K)");
+    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2,
+                "slide_tta_seg_update: ce_sums must be float64[2]");
+    c10::DeviceGuard g(l0.device());
+    const int64_t H = labels.size(1), W = labels.size(2);
+    Tensor pred = want_pred ? at::empty({l0.size(0), H, W}, like(l0, at::kByte)) : Tensor();
+    Tensor cnt = at::zeros({1}, like(l0, at::kLong));
+    Tensor ws = slide_tta_ws(l0, K, t);
+    DCLIP_CALL(dclip_slide_tta_eval_seg(dt_code(l0.scalar_type()), t.views.data(), (int)t.views.size(), t.wins.data(),
+                                        (int)t.wins.size(), (int)l0.size(0), (int)K, probs ? 1 : 0, labels.data_ptr(),
+                                        lab_code(labels.scalar_type()), (int)H, (int)W, (int)ignore_index,
+                                        ptr<uint8_t>(pred), ptr<int64_t>(cm), ptr<double>(ce_sums),
+                                        (unsigned long long*)cnt.data_ptr(), ws.data_ptr(), stream_of(l0)));
+    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
+    if (!want_pred) return c10::nullopt;
+    return pred;
+}
+
+// f32 (B, 1, H, W): the mean over the views of their depth slide results resized to H x W
+Tensor slide_tta_depth(at::TensorList preds, at::IntArrayRef views, at::IntArrayRef origins, int64_t H, int64_t W) {
+    const SlideTtaTables t = slide_tta_tables(preds, views, origins, true, "slide_tta_depth");
+    const Tensor& p0 = preds[0];
+    c10::DeviceGuard g(p0.device());
+    Tensor up = at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat));
+    Tensor ws = slide_tta_ws(p0, 1, t);
+    DCLIP_CALL(dclip_slide_tta_eval_depth(dt_code(p0.scalar_type()), t.views.data(), (int)t.views.size(), t.wins.data(),
+                                          (int)t.wins.size(), (int)p0.size(0), nullptr, nullptr, (int)H, (int)W, 0.f,
+                                          0.f, 0, 0.f, ptr<float>(up), nullptr, ws.data_ptr(), stream_of(p0)));
+    return up;
+}
+
+// depth_update on that mean
+c10::optional<Tensor> slide_tta_depth_update(at::TensorList preds, at::IntArrayRef views, at::IntArrayRef origins,
+                                             const Tensor& target, const c10::optional<Tensor>& mask, double min_depth,
+                                             double max_depth, bool clamp_pred, double eps, Tensor& sums,
+                                             bool want_up) {
+    const SlideTtaTables t = slide_tta_tables(preds, views, origins, true, "slide_tta_depth_update");
+    const Tensor& p0 = preds[0];
+    check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
+    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == p0.size(0),
+                "slide_tta_depth_update: target (B, H, W) fp32");
+    const bool has_mask = mask.has_value() && mask->defined();
+    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()),
+                "slide_tta_depth_update: mask (B, H, W) uint8");
+    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12,
+                "slide_tta_depth_update: sums must be float64[12]");
+    c10::DeviceGuard g(p0.device());
+    const int64_t H = target.size(1), W = target.size(2);
+    Tensor up = want_up ? at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat)) : Tensor();
+    Tensor ws = slide_tta_ws(p0, 1, t);
+    DCLIP_CALL(dclip_slide_tta_eval_depth(dt_code(p0.scalar_type()), t.views.data(), (int)t.views.size(), t.wins.data(),
+                                          (int)t.wins.size(), (int)p0.size(0), ptr<float>(target), optr<uint8_t>(mask),
+                                          (int)H, (int)W, (float)min_depth, (float)max_depth, clamp_pred ? 1 : 0,
+                                          (float)eps, ptr<float>(up), ptr<double>(sums), ws.data_ptr(),
+                                          stream_of(p0)));
+    if (!want_up) return c10::nullopt;
+    return up;
+}
+
 // ----------------------------------------------------------------------------- optimizer
 // dclip_adamw_* (optim.hip): desc (n, 12) int64 on the GPU, desc_host the same table on the CPU,
 // grads the f32 gradients in entry order (an undefined / empty tensor: no gradient this step)
@@ -1366,9 +1498,21 @@ TORCH_LIBRARY(dclip_eval, m) {
     m.def("slide_depth(Tensor[] preds, int[] origins, int wh, int ww, int H, int W) -> Tensor");
     m.def("slide_depth_update(Tensor[] preds, int[] origins, int wh, int ww, Tensor target, Tensor? mask, "
           "float min_depth, float max_depth, bool clamp_pred, float eps, Tensor(a!) sums, bool want_up) -> Tensor?");
+    // the same on the mean over V views of their sliding-window results (headslidetta.hip); logits / preds = every
+    // view's windows in view order, views = Hv, Wv, flip, wh, ww, nwin, ...; origins = y0, x0, ... in the view
+    m.def("slide_tta_argmax(Tensor[] logits, int[] views, int[] origins, int H, int W, bool probs) -> Tensor");
+    m.def("slide_tta_seg_update(Tensor[] logits, int[] views, int[] origins, Tensor labels, int ignore_index, "
+          "bool probs, Tensor(a!) cm, Tensor(b!) ce_sums, bool want_pred) -> Tensor?");
+    m.def("slide_tta_depth(Tensor[] preds, int[] views, int[] origins, int H, int W) -> Tensor");
+    m.def("slide_tta_depth_update(Tensor[] preds, int[] views, int[] origins, Tensor target, Tensor? mask, "
+          "float min_depth, float max_depth, bool clamp_pred, float eps, Tensor(a!) sums, bool want_up) -> Tensor?");
 }
 
 TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
+    m.impl("slide_tta_argmax", &slide_tta_argmax);
+    m.impl("slide_tta_seg_update", &slide_tta_seg_update);
+    m.impl("slide_tta_depth", &slide_tta_depth);
+    m.impl("slide_tta_depth_update", &slide_tta_depth_update);
     m.impl("upsample_argmax", &upsample_argmax);
     m.impl("seg_update", &seg_update);
     m.impl("depth_update", &depth_update);

@@ -30,6 +30,13 @@ slide_inference) likewise: `forward_windows` runs the model on the overlapping c
 `slide_windows` and keeps their low-res maps, and `predict_slide` / `Evaluator.update_windows` /
 `validate(..., slide=dict(crop_size=..., stride=...))` hand them to one fused kernel per head
 (csrc/headslide.hip) that averages, per pixel, the windows that cover it.
+
+The two combine as in mmseg's aug_test over slide_inference, the evaluation the reference's ViT
+configs run under --aug-test: `forward_view_windows` runs the windows of every scaled / mirrored view
+(`view_windows`), and `predict_slide_tta` / `Evaluator.update_view_windows` /
+`validate(..., slide_tta=dict(crop_size=..., stride=...))` hand all of them to one fused kernel per
+head (csrc/headslidetta.hip): per output pixel and view, up to four taps of the view's slide result,
+each the mean of its covering windows, with no per-view tensor.
 """
 import math
 
@@ -38,7 +45,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _torch_ops
-from ._native import SLIDE_MAX_WINDOWS
+from ._native import ENSEMBLE_MAX_VIEWS, SLIDE_MAX_WINDOWS, SLIDE_TTA_MAX_WINDOWS
 
 DEPTH_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 TTA_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)  # the reference's --aug-test ratios (test.py:93-96)
@@ -150,15 +157,20 @@ def slide_windows(H, W, crop_size, stride):
     max(H - ch + sh - 1, 0) // sh + 1 rows of windows (columns likewise); window (i, j) ends at
     y2 = min(i sh + ch, H) and starts at max(y2 - ch, 0), so every window is min(ch, H) x min(cw, W)
     and the last of a row or column is shifted back, not shrunk."""
+    return _slide_grid(H, W, crop_size, stride, SLIDE_MAX_WINDOWS)
+
+
+def _slide_grid(H, W, crop_size, stride, limit):
+    """`slide_windows` with the table's limit as an argument"""
     H, W = int(H), int(W)
     if H <= 0 or W <= 0:
         raise ValueError(f"slide: image size {H} x {W} must be positive")
     (ch, cw), (sh, sw) = _pair(crop_size, "crop_size"), _pair(stride, "stride")
     h_grids = max(H - ch + sh - 1, 0) // sh + 1
     w_grids = max(W - cw + sw - 1, 0) // sw + 1
-    if h_grids * w_grids > SLIDE_MAX_WINDOWS:
+    if h_grids * w_grids > limit:
         raise ValueError(f"slide: {h_grids} x {w_grids} = {h_grids * w_grids} windows on a {H} x {W} image with "
-                         f"crop_size={(ch, cw)}, stride={(sh, sw)} (at most {SLIDE_MAX_WINDOWS})")
+                         f"crop_size={(ch, cw)}, stride={(sh, sw)} (at most {limit})")
     origins = []
     for i in range(h_grids):
         for j in range(w_grids):
@@ -186,6 +198,13 @@ def forward_windows(model, img, crop_size, stride, windows_per_forward=None):
     batch."""
     H, W = _hw(img)
     (wh, ww), origins = slide_windows(H, W, crop_size, stride)
+    segs, depths = _forward_crops(model, img, (wh, ww), origins, windows_per_forward)
+    return segs or None, depths or None, (wh, ww), origins
+
+
+def _forward_crops(model, img, size, origins, windows_per_forward):
+    """the low-res maps (seg list, depth list) of `model` on the crops of `img` of `size` at `origins`"""
+    wh, ww = size
     n = 1 if windows_per_forward is None else int(windows_per_forward)
     if n <= 0:
         raise ValueError(f"slide: windows_per_forward={windows_per_forward!r} must be positive")
@@ -198,7 +217,7 @@ def forward_windows(model, img, crop_size, stride, windows_per_forward=None):
             for head, out in ((low["seg"], segs), (low["depth"], depths)):
                 if head is not None:
                     out.extend(c.contiguous() for c in head.detach().split(B, 0))
-    return segs or None, depths or None, (wh, ww), origins
+    return segs, depths
 
 
 def _flat(origins):
@@ -214,6 +233,64 @@ def predict_slide(model, img, crop_size, stride, windows_per_forward=None):
     E = _E()
     return {"seg": E.slide_argmax(segs, _flat(origins), wh, ww, H, W) if segs else None,
             "depth": E.slide_depth(depths, _flat(origins), wh, ww, H, W) if depths else None}
+
+
+def view_windows(H, W, crop_size, stride, scales=TTA_SCALES, flip=True):
+    """The windows of every view of mmseg's aug_test over slide_inference on an H x W image: a list,
+    in `tta_views` order, of (Hv, Wv, flipped, (wh, ww), origins) with (Hv, Wv) = (int(H s + 0.5),
+    int(W s + 0.5)) and `slide_windows(Hv, Wv, crop_size, stride)` in the view's own coordinates (a
+    mirrored view has the windows of the plain one: they are cut from the mirrored image).  At most
+    ENSEMBLE_MAX_VIEWS views and SLIDE_TTA_MAX_WINDOWS windows in all."""
+    H, W = int(H), int(W)
+    out = []
+    for s in scales:
+        Hv, Wv = int(H * s + 0.5), int(W * s + 0.5)
+        size, origins = _slide_grid(Hv, Wv, crop_size, stride, SLIDE_TTA_MAX_WINDOWS)
+        out.append((Hv, Wv, False, size, list(origins)))
+        if flip:
+            out.append((Hv, Wv, True, size, list(origins)))
+    total = sum(len(v[4]) for v in out)
+    if not out or len(out) > ENSEMBLE_MAX_VIEWS:
+        raise ValueError(f"slide_tta: {len(out)} views (1 .. {ENSEMBLE_MAX_VIEWS})")
+    if total > SLIDE_TTA_MAX_WINDOWS:
+        raise ValueError(f"slide_tta: {total} windows over {len(out)} views of a {H} x {W} image with "
+                         f"crop_size={crop_size!r}, stride={stride!r} (at most {SLIDE_TTA_MAX_WINDOWS})")
+    return out
+
+
+def forward_view_windows(model, img, crop_size, stride, scales=TTA_SCALES, flip=True, windows_per_forward=None):
+    """`model.forward_lowres` on every window (`view_windows`) of every view (`tta_views`) of `img` under
+    no_grad, one view's image at a time, keeping only the low-res maps: (seg_lows, depth_lows, views,
+    origins) with one list of (B, K, h_v, w_v) / (B, 1, h_v, w_v) maps per head over all views in view
+    order (None for a model without that head), views = [(Hv, Wv, flipped, wh, ww, nwin), ...] and
+    origins = [(y0, x0), ...] per window in its view's coordinates."""
+    H, W = _hw(img)
+    table = view_windows(H, W, crop_size, stride, scales, flip)
+    segs, depths, views, origins = [], [], [], []
+    for (view, flipped), (Hv, Wv, fl, size, orig) in zip(tta_views(img, scales, flip), table):
+        assert _hw(view) == (Hv, Wv) and flipped == fl
+        s, d = _forward_crops(model, view, size, orig, windows_per_forward)
+        segs.extend(s)
+        depths.extend(d)
+        views.append((Hv, Wv, int(flipped), size[0], size[1], len(orig)))
+        origins.extend(orig)
+    return segs or None, depths or None, views, origins
+
+
+def predict_slide_tta(model, img, crop_size, stride, scales=TTA_SCALES, flip=True, average="probs",
+                      windows_per_forward=None):
+    """`predict` under multi-scale + flip test-time augmentation with every view evaluated by sliding
+    windows (mmseg's aug_test over slide_inference): {'seg': uint8 (B, H, W), 'depth': fp32
+    (B, 1, H, W)} from the mean over the views of their slide results resized to the image and
+    mirrored back (csrc/headslidetta.hip: no per-view tensor).  `average`: 'probs' (mmseg's rule) or
+    'logits' for the class map; the depth is always the mean of the predictions."""
+    probs = _probs(average)
+    H, W = _hw(img)
+    segs, depths, views, origins = forward_view_windows(model, img, crop_size, stride, scales, flip,
+                                                        windows_per_forward)
+    E = _E()
+    return {"seg": E.slide_tta_argmax(segs, _flat(views), _flat(origins), H, W, probs) if segs else None,
+            "depth": E.slide_tta_depth(depths, _flat(views), _flat(origins), H, W) if depths else None}
 
 
 def metrics_from_sums(cm=None, ce_sums=None, depth_sums=None, lambd=0.5):
@@ -393,6 +470,51 @@ class Evaluator:
                 self.depth_sums += sums
         return own
 
+    def update_view_windows(self, seg_lows=None, depth_lows=None, views=(), origins=(), seg_target=None,
+                            depth_target=None, depth_mask=None, average="probs", per_call=False):
+        """`update` on one batch's windows of every view (`forward_view_windows`): lists of low-res maps
+        over all views in view order, views = [(Hv, Wv, flipped, wh, ww, nwin), ...] and the windows'
+        origins [(y0, x0), ...] in their view's coordinates; the metrics are taken from the mean over
+        the views of their slide results resized to the target's size and mirrored back (`average`:
+        'probs' or 'logits' for the class map and the CE).  Same contract as `update`: no host
+        synchronisation, no new tensor besides the workspace, added to the running state;
+        per_call=True returns the call's own sums."""
+        probs = _probs(average)
+        E = _E()
+        vflat, oflat = _flat(views), _flat(origins)
+        own = None
+        if per_call:
+            own = {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
+                   "depth_sums": torch.zeros_like(self.depth_sums)}
+        if seg_lows and seg_target is not None:
+            for v in seg_lows:
+                _need_gpu(v, "seg_lows")
+                if v.shape[1] != self.num_classes:
+                    raise ValueError(f"Evaluator: {v.shape[1]} classes, built for {self.num_classes}")
+            lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
+            if lab.dtype not in _LAB_DTYPES:
+                lab = lab.long()
+            cm, ce = (own["cm"], own["ce_sums"]) if per_call else (self.cm, self.ce_sums)
+            E.slide_tta_seg_update([v.detach().contiguous() for v in seg_lows], vflat, oflat, lab.contiguous(),
+                                   self.ignore_index, probs, cm, ce, False)
+            if per_call:
+                self.cm += cm
+                self.ce_sums += ce
+        if depth_lows and depth_target is not None:
+            for v in depth_lows:
+                _need_gpu(v, "depth_lows")
+            B = depth_target.shape[0]
+            tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
+            mk = None
+            if depth_mask is not None:
+                mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
+            sums = own["depth_sums"] if per_call else self.depth_sums
+            E.slide_tta_depth_update([v.detach().contiguous() for v in depth_lows], vflat, oflat, tg, mk,
+                                     self.min_depth, self.max_depth, self.clamp_pred, self.eps, sums, False)
+            if per_call:
+                self.depth_sums += sums
+        return own
+
     def all_reduce(self, group=None):
         """Sum the state over the ranks of `group`: one all_reduce per state tensor."""
         import torch.distributed as dist
@@ -409,7 +531,10 @@ class Evaluator:
                                  self.lambd)
 
 
-def validate(model, batches, evaluator=None, tta=None, slide=None, **loss_cfg):
+_SLIDE_TTA_KEYS = ("crop_size", "stride", "scales", "flip", "average", "windows_per_forward")
+
+
+def validate(model, batches, evaluator=None, tta=None, slide=None, slide_tta=None, **loss_cfg):
     """Evaluate `model` over `batches` of (img, seg, depth, mask) (train.synth_batch's layout) in
     eval mode under no_grad, restore the model's mode, and return `evaluator.compute()`.  Under an
     initialised process group the state is summed over the ranks first.  `tta`: None (one forward
@@ -418,9 +543,32 @@ def validate(model, batches, evaluator=None, tta=None, slide=None, **loss_cfg):
     `slide`: None, dict(crop_size=..., stride=...[, windows_per_forward=...]) for sliding-window
     inference (`forward_windows` + `update_windows`), or True to take crop_size and stride from
     `model.test_cfg` (which must then be dict(mode='slide', crop_size=..., stride=...)); `slide` and
-    `tta` do not combine.  `loss_cfg`: Evaluator keywords (lambd, eps, min_depth, ...) for the default
+    `tta` do not combine: `slide_tta` is their combination, mmseg's aug_test over slide_inference
+    (`forward_view_windows` + `update_view_windows`): dict(crop_size=..., stride=...[, scales=...,
+    flip=..., average=..., windows_per_forward=...]) (TTA_SCALES, True, 'probs'), or True to take
+    crop_size and stride from `model.test_cfg`; it excludes both `slide` and `tta`.  `loss_cfg`: Evaluator keywords (lambd, eps, min_depth, ...) for the default
     evaluator."""
     import torch.distributed as dist
+    if slide_tta is not None and slide_tta is not False:
+        if tta is not None or (slide is not None and slide is not False):
+            raise ValueError("validate: slide_tta is sliding windows over multi-scale + flip views by itself; it does "
+                             "not combine with slide or tta")
+        if slide_tta is True:
+            slide_tta = slide_from_test_cfg(getattr(model, "test_cfg", None))
+            if slide_tta is None:
+                raise ValueError(f"validate: slide_tta=True needs model.test_cfg = dict(mode='slide', crop_size=..., "
+                                 f"stride=...), got {getattr(model, 'test_cfg', None)!r}")
+        unknown = set(slide_tta) - set(_SLIDE_TTA_KEYS)
+        if unknown:
+            raise ValueError(f"validate: unknown slide_tta keys {sorted(unknown)} ({', '.join(_SLIDE_TTA_KEYS)})")
+        if "crop_size" not in slide_tta or "stride" not in slide_tta:
+            raise ValueError("validate: slide_tta needs crop_size and stride")
+        _pair(slide_tta["crop_size"], "crop_size"), _pair(slide_tta["stride"], "stride")
+        slide_tta = dict(slide_tta)
+        st_average = slide_tta.pop("average", "probs")
+        _probs(st_average)
+    else:
+        slide_tta = None
     if tta is not None:
         unknown = set(tta) - {"scales", "flip", "average"}
         if unknown:
@@ -431,7 +579,7 @@ def validate(model, batches, evaluator=None, tta=None, slide=None, **loss_cfg):
     if slide is not None and slide is not False:
         if tta is not None:
             raise ValueError("validate: slide and tta do not combine (sliding windows over multi-scale + flip views "
-                             "are not implemented)")
+                             "are validate(slide_tta=dict(crop_size=..., stride=..., ...)))")
         if slide is True:
             slide = slide_from_test_cfg(getattr(model, "test_cfg", None))
             if slide is None:
@@ -453,6 +601,10 @@ def validate(model, batches, evaluator=None, tta=None, slide=None, **loss_cfg):
             for img, seg, depth, mask in batches:
                 if evaluator is None:
                     evaluator = Evaluator(device=img.device, **loss_cfg)
+                if slide_tta is not None:
+                    segs, depths, views, origins = forward_view_windows(model, img, **slide_tta)
+                    evaluator.update_view_windows(segs, depths, views, origins, seg, depth, mask, average=st_average)
+                    continue
                 if tta is not None:
                     segs, depths, flips = forward_views(model, img, scales, flip)
                     evaluator.update_views(segs, depths, flips, seg, depth, mask, average=average)

@@ -32,6 +32,8 @@
  *                              utils/depth_metrics.py:12-88
  *   dclip_slide_eval_seg/depth test_cfg mode='slide' of configs/denseclip_fpn_vit-b_640x640_80k.py:51 (the
  *                              rule is mmseg's slide_inference, restated at the entry points)
+ *   dclip_slide_tta_eval_seg/depth  the same under test.py:91-96 --aug-test (mmseg's aug_test over
+ *                              slide_inference: every scaled / mirrored view evaluated with windows)
  *   dclip_adamw_prepare/update torch.optim.AdamW.step + clip_grad_norm_ + the 1/grad_accum_steps loss scaling,
  *                              train_denseclip.py:1061, 1154-1155, 1314, 1356-1358
  *   dclip_im2col               conv1 (16x16, stride 16, no bias) models.py:407,546
@@ -491,6 +493,54 @@ int dclip_slide_eval_seg(int low_dt, const dclip_window* wins, int nwin, int B, 
 int dclip_slide_eval_depth(int low_dt, const dclip_window* wins, int nwin, int B, int h, int w, int wh, int ww,
                            const float* target, const uint8_t* mask, int H, int W, float min_depth, float max_depth,
                            int clamp_pred, float eps, float* up, double* sums, void* ws, void* stream);
+
+/* Sliding windows inside multi-scale + flip ensembling: mmseg's aug_test -> inference ->
+ * slide_inference, what the reference's ViT configs (test_cfg mode='slide') run under test.py
+ * --aug-test, without any per-view tensor (no (B, K, Hv, Wv) accumulator, count map, resized or
+ * softmax copy).  View v is the image resized to Hv x Wv (Hv > H allowed) and mirrored when flip; it
+ * is evaluated with the windows wins[first .. first + nwin) of one size wh x ww in the VIEW's
+ * coordinates, each a low-res map (B, K, h, w) of low_dt (one h x w per view; one dtype, B and K for
+ * the call) at origin (y0, x0) of the view.  Per output pixel (y, x), for every view in the order given:
+ *   S_v, the view's slide result, is per view pixel what dclip_slide_eval_* computes on an Hv x Wv
+ *       image: the resizes of the covering windows' maps to wh x ww, accumulated in f32 in table
+ *       order, and one correctly rounded division by their number;
+ *   U_v = the bilinear resize (align_corners=False, plain 4 taps, no antialiasing; the fused
+ *       multiply-adds of dclip_ensemble_eval_seg) of S_v to H x W at (y, x_v), x_v = x for a plain
+ *       view and W-1-x for a flipped one; (Hv, Wv) == (H, W): U_v = S_v(y, x_v), no arithmetic;
+ *   the U_v (average 0, "logits") or softmax_K(U_v) (average 1, "probs", mmseg's rule here) are
+ *       accumulated in f32 in view order and scaled by 1/nviews, CE as dclip_ensemble_eval_seg; the
+ *       depth is always the mean of the U_v.
+ * pred / labels / cm / loss_sum / count / up / sums / target / mask are dclip_slide_eval_*'s, taken
+ * from that mean; without labels cm, loss_sum and count must be null (pred required); without a
+ * target up is required.  Both tables are HOST arrays: nviews in 1 .. DCLIP_ENSEMBLE_MAX_VIEWS,
+ * nwin_total in 1 .. DCLIP_SLIDE_TTA_MAX_WINDOWS.  The window table does not fit kernel arguments:
+ * the call writes it into ws with small launches of its own (no copy, no pinned memory), so it
+ * stays stream-ordered and capturable, and ws is ALWAYS required: dclip_slide_tta_eval_ws_bytes(B, K,
+ * nviews, nwin_total) bytes (K = 1 for depth; a function of its arguments alone), 8-byte aligned,
+ * contents undefined on entry.  Checked on the host before any launch: K == 19; h <= wh <= Hv,
+ * w <= ww <= Wv, 0 <= y0 <= Hv - wh, 0 <= x0 <= Wv - ww; every view pixel covered (the message names
+ * the view and its first uncovered pixel); B*H*W and B*Hv*Wv < 2^31; a window's patch under one
+ * output tile within the kernel's LDS (views up to a few times the image).  Reductions as
+ * dclip_upsample_eval_*: exact counts, f64 sums in a fixed order, two runs bitwise equal, no atomics on
+ * global memory.  Additive to ABI 7.  Degenerate cases, bitwise:
+ *   one plain view at the image's size = dclip_slide_eval_* on the same windows (pred, cm, count;
+ *       up and the 12 depth sums; the CE sum only to rounding, its summation order differs);
+ *   views at the image's size with one window over the whole view each = dclip_ensemble_eval_* on
+ *       the same maps (likewise);
+ *   a flipped view = the column mirror of the same view unflipped.  */
+#define DCLIP_SLIDE_TTA_MAX_WINDOWS 1024 /* total over the views; views <= DCLIP_ENSEMBLE_MAX_VIEWS */
+typedef struct {
+    int Hv, Wv, flip, wh, ww, h, w, first, nwin; /* wins[first .. first+nwin) */
+} dclip_slide_view;
+int64_t dclip_slide_tta_eval_ws_bytes(int B, int K, int nviews, int nwin_total);
+int dclip_slide_tta_eval_seg(int low_dt, const dclip_slide_view* views, int nviews, const dclip_window* wins,
+                             int nwin_total, int B, int K, int average, const void* labels, int lab_dt, int H, int W,
+                             int ignore_index, uint8_t* pred, int64_t* cm, double* loss_sum,
+                             unsigned long long* count, void* ws, void* stream);
+int dclip_slide_tta_eval_depth(int low_dt, const dclip_slide_view* views, int nviews, const dclip_window* wins,
+                               int nwin_total, int B, const float* target, const uint8_t* mask, int H, int W,
+                               float min_depth, float max_depth, int clamp_pred, float eps, float* up, double* sums,
+                               void* ws, void* stream);
 
 /* Cityscapes depth + segmentation batch preparation (datasets/cityscapes_depth_seg.py:129-170,
  * 218 and the trainer's RandomCrop / HorizontalFlip / Normalize / ToTensorV2,
