@@ -322,7 +322,12 @@ int dclip_score_map(const void* v, int v_dt, int64_t bstride, int64_t row_off, i
 int dclip_score_concat(const void* rows, int dt, int64_t bstride, int64_t row_off, int64_t ld, int C,
                        const float* score, int K, int hs, int ws, void* out, int B, int h, int w, void* stream);
 
-/* Bilinear resize, align_corners=False, of NC planes (NC, Hi, Wi) -> (NC, Ho, Wo).   */
+/* Bilinear resize, align_corners=False, of NC planes (NC, Hi, Wi) -> (NC, Ho, Wo).  Every
+ * bilinear entry point (this pair, dclip_pos_interp_*, dclip_score_concat) takes its weights
+ * from PyTorch's index formula in f32: scale = in / out, src = max(scale * (dst + .5) - .5, 0)
+ * with the multiply-subtract FUSED (rounded once, as PyTorch's own kernels are compiled; rounding
+ * the product first moves src by an ulp at a fifth of the columns of a 5 -> 1028 resize), i0 =
+ * (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1; equal sizes copy exactly.   */
 int dclip_bilinear_fwd(const void* in, int in_dt, void* out, int out_dt,
                        int64_t NC, int Hi, int Wi, int Ho, int Wo, void* stream);
 /* Its gradient: din f32 (NC, Hi, Wi) = resize^T(dout).  ws: f32 (NC, Ho, Wi).        */

@@ -1,5 +1,5 @@
 """Guard-banded, poisoned buffers for tests that call the C ABI directly (test_gpu_abi_contract.py,
-test_gpu_gemm_contract.py, test_gpu_conv_contract.py).
+test_gpu_gemm_contract.py, test_gpu_conv_contract.py, test_gpu_misc_contract.py).
 
 The op layer allocates every output and workspace with at::empty, and the caching allocator hands a
 second call the block the first one just freed — still holding the first call's (correct) result.
@@ -19,7 +19,7 @@ caller's choice, so that
 Workspaces are sized by the library's own queries, never smaller.
 A matrix with a leading dimension larger than its width (guarded_matrix) ends at its last valid
 element; its gap columns hold NaN when it is an input and must come back untouched when it is an
-output.
+output.  GuardedStrided is the same for any strided view: batches of matrices, strided pixel rows.
 """
 import contextlib
 
@@ -98,6 +98,45 @@ def guarded_matrix_copy(t, ld):
     g = GuardedMatrix(t.shape[0], t.shape[1], ld, t.dtype, POISON)
     g.m.copy_(t)
     return g
+
+
+class GuardedStrided(Guarded):
+    """A tensor of `shape` with arbitrary non-overlapping `strides` (in elements) starting `offset`
+    elements into a guarded payload that ends at the view's last element: a batch of matrices with a
+    batch stride and a leading dimension, or the library's strided pixel rows (guarded_rows_copy).
+    `t`: the whole payload (flat), filled with `fill` throughout (0xFF for an input: whatever lies
+    between the valid elements holds NaN); `m`: the strided view; `gap`: the payload's elements
+    outside `m` (a copy, in order), which an output must bring back untouched."""
+
+    def __init__(self, shape, strides, dtype, fill=0, offset=0):
+        shape, strides = tuple(int(s) for s in shape), tuple(int(s) for s in strides)
+        assert len(shape) == len(strides) and min(shape) >= 1 and min(strides) >= 1 and offset >= 0
+        super().__init__(int(offset) + sum((n - 1) * s for n, s in zip(shape, strides)) + 1, dtype, fill)
+        self.m = self.t.as_strided(shape, strides, self.t.storage_offset() + int(offset))  # absolute in the storage
+        outside = torch.ones(self.t.shape, dtype=torch.bool, device=self.t.device)
+        outside.as_strided(shape, strides, int(offset)).fill_(False)
+        assert int(outside.numel() - outside.sum()) == self.m.numel(), "overlapping strides"
+        self._outside = outside
+
+    @property
+    def gap(self):
+        return self.t[self._outside]
+
+
+def guarded_strided_copy(t, strides, offset=0):
+    """`t`'s values at `strides` from `offset`, NaN everywhere else and behind the last element"""
+    g = GuardedStrided(t.shape, strides, t.dtype, POISON, offset)
+    g.m.copy_(t)
+    return g
+
+
+def guarded_rows_copy(t, ld, row_off):
+    """The (batch, rows, cols) tensor `t` as the library's strided pixel rows: row r of image b at
+    b * bstride + (row_off + r) * ld, bstride = (row_off + rows) * ld.  row_off = 1, ld = cols is a
+    ViT token buffer whose CLS rows are skipped (they hold NaN here); row_off = 0, ld > cols a
+    channel slice of a wider map.  Returns (buffer, bstride); the layout's base is buffer.ptr()."""
+    bstride = (row_off + t.shape[1]) * ld
+    return guarded_strided_copy(t, (bstride, ld, 1), row_off * ld), bstride
 
 
 def valid(g):
