@@ -1,5 +1,7 @@
 """The cases, references, bounds and plain-torch emulations of test_gpu_misc_contract.py (every kernel
-of csrc/misc.hip but dclip_weight_refresh and the fp16-scaling entry points), on CPU tensors, so
+of csrc/misc.hip but dclip_weight_refresh and the fp16-scaling entry points dclip_grad_scale,
+dclip_add_readout_cast / _amax / _cast_scaled and dclip_row_scale_add, which norm_check.py and
+test_gpu_norm_contract.py hold to the same kind of contract), on CPU tensors, so
 that the emulation goes through the very same checker (test_misc_contract_emulation_cpu.py) before
 any kernel does.  Conventions of gemm_check.py: every reference in fp64 from the operands as
 rounded to their storage dtype, p = 11 / 8 / 24 for fp16 / bf16 / f32 outputs, u = 2^-24, no share

@@ -1,6 +1,7 @@
 """Every kernel of csrc/misc.hip behind the C ABI (im2col, token assembly, positional-embedding and
 bilinear resize, transposes, the row mean, the pixel-text score map, score concatenation, casts,
-BatchNorm; not dclip_weight_refresh nor the fp16-scaling entry points of test_gpu_fp16.py) on
+BatchNorm; not dclip_weight_refresh, nor the fp16-scaling entry points: test_gpu_norm_contract.py
+holds those to the same kind of contract) on
 guard-banded, poisoned, strided buffers (abi_guard.py), every output against an fp64 reference per
 element or bit for bit (misc_check.py: the cases, the references, the bounds and why they hold).
 
