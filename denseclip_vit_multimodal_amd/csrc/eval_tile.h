@@ -1,10 +1,16 @@
-// The tile machinery shared by the fused head evaluation kernels (headeval.hip: one low-res map per
-// output pixel; headensemble.hip: V of them; headslide.hip: the windows that cover it;
-// headslidetta.hip: the windows of V views): the resize's
-// source index, the low-res patch of an 8 x TW output tile and its LDS staging, the interpolation
-// with its fused multiply-adds spelled out (the ensemble's and the sliding windows'), the windows'
-// rounded division and host-side coverage check, the 4-pixel
-// label load, the per-workgroup record in the caller's workspace and the one-workgroup folds.
+// What the fused head evaluation kernels share (headeval.hip: one low-res map per output pixel;
+// headensemble.hip: V of them; headslide.hip: the windows that cover it; headslidetta.hip: the
+// windows of V views).  Each kernel keeps what is its own: the patches it stages, its taps, its
+// slot-to-pixel map and its accumulation over views / windows.  Here:
+//   * before the values: the resize's source index, the tile's origin and low-res patch and its LDS
+//     staging, the interpolation with its fused multiply-adds spelled out, the windows' rounded
+//     division and host-side coverage check;
+//   * after them, the scoring epilogue, once: the 4-pixel label load, argmax / CE / confusion counts
+//     (seg_score), the depth terms (DepthSums), the class-map and depth-map stores, the per-workgroup
+//     record in the caller's workspace and the one-workgroup folds;
+//   * the host side the four files repeat: the tiling's tail, the alignment flags, the argument
+//     checks of the labels-given / labels-absent and target-given / target-absent calls, the
+//     dispatch on the low-res dtype.
 // Everything here has internal linkage: each translation unit that includes it compiles its own copy.
 #pragma once
 #include <algorithm>
@@ -53,6 +59,24 @@ struct Tiling {
     int tw, nrow, ncol, tiles_x, tiles_y, ntiles, nwg;
     size_t lds;
 };
+// the grid of 8 x t.tw tiles over B images of H x W, walked by at most NWG_MAX workgroups
+inline void finish_tiling(Tiling& t, int B, int H, int W) {
+    t.tiles_x = (W + t.tw - 1) / t.tw;
+    t.tiles_y = (H + TH - 1) / TH;
+    t.ntiles = B * t.tiles_y * t.tiles_x;  // < 2^31: B * H * W is
+    t.nwg = t.ntiles < NWG_MAX ? t.ntiles : NWG_MAX;
+}
+
+struct TileOrigin {
+    int b, y0, x0;
+};
+__device__ __forceinline__ TileOrigin tile_origin(int tile, const Tiling& tl) {
+    TileOrigin o;
+    o.b = tile / (tl.tiles_x * tl.tiles_y);
+    o.y0 = ((tile / tl.tiles_x) % tl.tiles_y) * TH;
+    o.x0 = (tile % tl.tiles_x) * tl.tw;
+    return o;
+}
 
 // the tile's low-res patch -> LDS: rows [ilo, ilo + nr) x columns [jlo, jlo + nc) of every channel
 template <typename TL>
@@ -68,34 +92,34 @@ __device__ __forceinline__ void stage_patch(float* __restrict__ low_s, const TL*
 struct TileGeom {
     int b, y0, x0, ilo, nr, jlo, nc;
 };
-__device__ __forceinline__ TileGeom tile_geom(int tile, int tiles_x, int tiles_y, int tw, int h, int w, int H, int W,
-                                              int nrow, int ncol) {
+__device__ __forceinline__ TileGeom tile_geom(int tile, const Tiling& tl, int h, int w, int H, int W) {
+    const TileOrigin o = tile_origin(tile, tl);
     TileGeom g;
-    g.b = tile / (tiles_x * tiles_y);
-    g.y0 = ((tile / tiles_x) % tiles_y) * TH;
-    g.x0 = (tile % tiles_x) * tw;
+    g.b = o.b;
+    g.y0 = o.y0;
+    g.x0 = o.x0;
     const int y1 = g.y0 + TH - 1 < H ? g.y0 + TH - 1 : H - 1;
-    const int x1 = g.x0 + tw - 1 < W ? g.x0 + tw - 1 : W - 1;
+    const int x1 = g.x0 + tl.tw - 1 < W ? g.x0 + tl.tw - 1 : W - 1;
     g.ilo = lerp_index(g.y0, h, H).i0;
     g.jlo = lerp_index(g.x0, w, W).i0;
     g.nr = lerp_index(y1, h, H).i1 - g.ilo + 1;
     g.nc = lerp_index(x1, w, W).i1 - g.jlo + 1;
-    g.nr = g.nr < nrow ? g.nr : nrow;  // low_span() bounds both; never index LDS past the patch
-    g.nc = g.nc < ncol ? g.nc : ncol;
+    g.nr = g.nr < tl.nrow ? g.nr : tl.nrow;  // low_span() bounds both; never index LDS past the patch
+    g.nc = g.nc < tl.ncol ? g.nc : tl.ncol;
     return g;
 }
 
-// One interpolated value, with every fused multiply-add spelled out.  headeval.hip leaves
-// Y.l0 * (X.l0 * a00 + X.l1 * a01) + Y.l1 * (...) to the compiler's contraction, and the compiler
-// does not fuse a thread's four pixels (slots) alike.  Here a flipped view must be the exact mirror
-// of the plain one, and a pixel and its mirror sit in different slots, so the roundings are fixed.
-//   bilerp:       the form of most of headeval's slots, for every slot (the segmentation kernel).
-//   bilerp_depth: the forms eval_depth_kernel compiles to on gfx950, per slot, read from its
-//                 assembly: slot 0 fuses the outer sum on the bottom row, slot 1 the top row's sum
-//                 on its right tap, everything else as bilerp.  With these, one plain view is
-//                 bitwise dclip_upsample_eval_depth (test_gpu_tta.py pins it; a compiler that fuses
-//                 headeval.hip otherwise shows up there).  The depth kernel keeps a source column
-//                 in the slot column % 4, flipped or not, so the mirror stays exact.
+// One interpolated value, with every fused multiply-add spelled out: the definition of the resize's
+// arithmetic, not left to the compiler's contraction, which does not fuse a thread's four pixels
+// (slots) alike.  A flipped view must be the exact mirror of the plain one, and a pixel and its
+// mirror sit in different slots, so the roundings are fixed.
+//   bilerp:       one form for every slot (the segmentation kernels of the ensemble and the windows;
+//                 eval_seg_kernel alone still leaves its interpolation to contraction).
+//   bilerp_depth: the depth's form, for all four depth kernels: slot 0 fuses the outer sum on the
+//                 bottom row, slot 1 the top row's sum on its right tap, everything else as bilerp.
+//                 The slot is the source column % 4 (window-local under windows), flipped or not, so
+//                 the mirror stays exact and one plain view is bitwise dclip_upsample_eval_depth
+//                 (test_gpu_tta.py holds it).
 __device__ __forceinline__ float bilerp(float yl0, float yl1, float xl0, float xl1, float a00, float a01, float a10,
                                         float a11) {
 #pragma clang fp contract(off)
@@ -213,6 +237,171 @@ __device__ __forceinline__ void wg_partials(double (&a)[N], double* __restrict__
     }
 }
 
+// ----------------------------------------------------------------------------- segmentation epilogue
+// the workgroup's LDS histogram (K x K confusion cells + #valid) starts at zero
+template <int K>
+__device__ __forceinline__ void hist_clear(unsigned* __restrict__ hist_s) {
+    for (int e = threadIdx.x; e < K * K + 1; e += blockDim.x) hist_s[e] = 0u;
+    __syncthreads();
+}
+
+// Scores PX consecutive pixels of one row from their K values v (already the mean its caller
+// scores): am[p] = argmax, the lowest class index among equal maxima (torch.argmax).  LAB: with the
+// labels t[p] (pixels p >= n lie outside the row), lsum += the CE terms in pixel order,
+// -log softmax(v)[t], or -log v[t] when v holds mean probabilities (PROBS), and the (target,
+// prediction) cells are counted in hist_s.
+template <int K, int PX, bool LAB, bool PROBS>
+__device__ __forceinline__ void seg_score(const float (&v)[PX][K], const int* t, int n, int ignore,
+                                          unsigned* __restrict__ hist_s, double& lsum, int (&am)[PX]) {
+    int cell_prev = -1;
+    unsigned run = 0;
+#pragma unroll
+    for (int p = 0; p < PX; ++p) {
+        float m = v[p][0];
+        int a = 0;
+#pragma unroll
+        for (int k = 1; k < K; ++k)
+            if (v[p][k] > m) {
+                m = v[p][k];
+                a = k;
+            }
+        am[p] = a;
+        if constexpr (LAB) {
+            const int tp = t[p];
+            const bool valid = p < n && tp != ignore && tp >= 0 && tp < K;
+            if (valid) {
+                float vt = 0.f, s = 0.f;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    vt = k == tp ? v[p][k] : vt;
+                    if constexpr (!PROBS) s += __expf(v[p][k] - m);
+                }
+                if constexpr (PROBS) lsum += (double)(-__logf(vt));
+                else lsum += (double)(__logf(s) - (vt - m));  // as dclip_upsample_ce
+            }
+            // runs of equal (target, prediction) cells among the pixels: one LDS add each
+            const int cell = valid ? tp * K + a : -1;
+            if (cell != cell_prev) {
+                if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
+                cell_prev = cell;
+                run = 0;
+            }
+            ++run;
+        }
+    }
+    if constexpr (LAB) {
+        if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
+    }
+}
+
+// 4 class ids of one row; `vec`: the row segment is aligned for one dword
+__device__ __forceinline__ void store_pred4(uint8_t* __restrict__ pred, int64_t pix, int n, bool vec,
+                                            const int (&am)[4]) {
+    if (pred == nullptr) return;
+    if (vec) {
+        *(uint32_t*)(pred + pix) =
+            (uint32_t)am[0] | ((uint32_t)am[1] << 8) | ((uint32_t)am[2] << 16) | ((uint32_t)am[3] << 24);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (p < n) pred[pix + p] = (uint8_t)am[p];
+    }
+}
+
+// the workgroup's record: its CE partial, #valid and its histogram
+template <int K>
+__device__ __forceinline__ void seg_flush(const unsigned* __restrict__ hist_s, double lsum, double* __restrict__ red_s,
+                                          char* __restrict__ ws) {
+    char* rec = ws + (int64_t)blockIdx.x * record_bytes(K);
+    double a[1] = {lsum};
+    wg_partials<1>(a, red_s, (double*)rec);  // __syncthreads inside: every LDS add has landed after it
+    unsigned* hist = (unsigned*)(rec + NSUM * 8);
+    if (threadIdx.x == 0) {
+        unsigned c = 0;
+        for (int e = 0; e < K * K; ++e) c += hist_s[e];
+        hist[K * K] = c;  // #valid
+    }
+    for (int e = threadIdx.x; e < K * K; e += blockDim.x) hist[e] = hist_s[e];
+}
+
+// ----------------------------------------------------------------------------- depth epilogue
+// 4 resized depths of one row; `vec`: the row segment is aligned for one vector store
+__device__ __forceinline__ void store_up4(float* __restrict__ up, int64_t pix, int n, bool vec, const float (&u)[4]) {
+    if (up == nullptr) return;
+    if (vec) {
+        *(float4*)(up + pix) = make_float4(u[0], u[1], u[2], u[3]);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (p < n) up[pix + p] = u[p];
+    }
+}
+
+// A thread's share of the 12 sums of dclip.h: sums[1..4], [9..11] in f64, in the order its pixels are
+// scored; the counts [0], [5..8] as integers (exact), widened at the end.
+struct DepthSums {
+    double s_sq = 0.0, s_log = 0.0, s_abs = 0.0, s_sqrel = 0.0, s_msq = 0.0, s_d = 0.0, s_d2 = 0.0;
+    unsigned n_eval = 0, n_a1 = 0, n_a2 = 0, n_a3 = 0, n_mask = 0;
+
+    // 4 pixels of one row with the resized predictions u; `vec`: gt and mask are aligned for one
+    // vector load each
+    __device__ __forceinline__ void score4(const float (&u)[4], const float* __restrict__ gt,
+                                           const uint8_t* __restrict__ mask, int64_t pix, int n, bool vec, float dmin,
+                                           float dmax, int clamp_pred, float eps) {
+        float tg[4] = {0.f, 0.f, 0.f, 0.f};
+        bool tm[4];
+        if (vec) {
+            const float4 a = *(const float4*)(gt + pix);
+            tg[0] = a.x; tg[1] = a.y; tg[2] = a.z; tg[3] = a.w;
+            const uint32_t mk = mask ? *(const uint32_t*)(mask + pix) : 0x01010101u;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) tm[p] = ((mk >> (8 * p)) & 0xffu) != 0;
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                tm[p] = false;
+                if (p < n) {
+                    tg[p] = gt[pix + p];
+                    tm[p] = mask == nullptr || mask[pix + p] != 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            if (!tm[p]) continue;
+            const float gtv = tg[p];
+            // the trainer's masked RMSE (unclamped) and the SILog pass-0 sums, d as dclip_upsample_silog
+            ++n_mask;
+            const float dm = gtv - u[p];
+            s_msq += (double)(dm * dm);
+            const float d = logf(fmaxf(u[p], eps)) - logf(fmaxf(gtv, eps));
+            s_d += (double)d;
+            s_d2 += (double)d * (double)d;
+            // compute_depth_errors: mask && min <= gt <= max, optionally clamped prediction
+            if (!(gtv >= dmin && gtv <= dmax)) continue;
+            const float pr = clamp_pred ? fminf(fmaxf(u[p], dmin), dmax) : u[p];
+            ++n_eval;
+            const float thr = fmaxf(gtv / pr, pr / gtv);
+            n_a1 += thr < 1.25f ? 1u : 0u;
+            n_a2 += thr < 1.5625f ? 1u : 0u;
+            n_a3 += thr < 1.953125f ? 1u : 0u;
+            const float df = gtv - pr;
+            const float dl = logf(gtv) - logf(pr);
+            s_sq += (double)(df * df);
+            s_log += (double)(dl * dl);
+            s_abs += (double)(fabsf(df) / gtv);
+            s_sqrel += (double)(df * df / gtv);
+        }
+    }
+
+    // the workgroup's record: its 12 partials
+    __device__ __forceinline__ void flush(double* __restrict__ red_s, char* __restrict__ ws) const {
+        double a[NSUM] = {(double)n_eval, s_sq,          s_log,          s_abs, s_sqrel, (double)n_a1,
+                          (double)n_a2,   (double)n_a3, (double)n_mask, s_msq, s_d,     s_d2};
+        wg_partials<NSUM>(a, red_s, (double*)(ws + (int64_t)blockIdx.x * record_bytes(1)));
+    }
+};
+
 // cm / count / loss_sum += the workgroups' records, in workgroup order
 __global__ __launch_bounds__(256) void eval_seg_fold_kernel(const char* __restrict__ ws, int nwg, int K,
                                                             int64_t* __restrict__ cm, double* __restrict__ loss_sum,
@@ -261,5 +450,55 @@ __global__ __launch_bounds__(256) void eval_depth_fold_kernel(const char* __rest
     }
     if (t < NSUM) sums[t] += red[t][0];
 }
+
+// ----------------------------------------------------------------------------- host side
+// whether the 4-pixel row segments of an image of width W are aligned for one vector access
+inline int labels_aligned(const void* lab, int lab_dt, int W) {
+    const int lab_align = lab_dt == 0 ? 16 : lab_dt == 1 ? 16 : 4;
+    return lab != nullptr && W % 4 == 0 && (uintptr_t)lab % lab_align == 0;
+}
+inline int pred_aligned(const uint8_t* pred, int W) {
+    return pred != nullptr && W % 4 == 0 && (uintptr_t)pred % 4 == 0;
+}
+inline int depth_aligned(const float* gt, const uint8_t* mask, const float* up, int W) {
+    return W % 4 == 0 && (gt == nullptr || (uintptr_t)gt % 16 == 0) && (mask == nullptr || (uintptr_t)mask % 4 == 0) &&
+           (up == nullptr || (uintptr_t)up % 16 == 0);
+}
+
+// the outputs of a segmentation entry point `name`: with labels, or the class map alone
+inline int check_seg_outputs(const char* name, const void* labels, int lab_dt, const uint8_t* pred, const int64_t* cm,
+                             const double* loss_sum, const unsigned long long* count) {
+    if (labels != nullptr) {
+        DCLIP_HOST_CHECK(lab_dt >= 0 && lab_dt <= 2, "%s: lab_dt=%d: labels int64 (0), int32 (1) or uint8 (2)", name,
+                         lab_dt);
+        DCLIP_HOST_CHECK(cm && loss_sum && count, "%s: cm, loss_sum and count required with labels", name);
+    } else {
+        DCLIP_HOST_CHECK(!cm && !loss_sum && !count, "%s: cm, loss_sum and count must be null without labels", name);
+        DCLIP_HOST_CHECK(pred != nullptr, "%s: nothing to do (no labels, no pred)", name);
+    }
+    return 0;
+}
+// the outputs of a depth entry point `name` whose target is optional: without one (prediction only)
+// mask and sums are not touched
+inline int check_depth_outputs(const char* name, const float* target, const double* sums, const float* up) {
+    if (target != nullptr) DCLIP_HOST_CHECK(sums != nullptr, "%s: sums required with a target", name);
+    else DCLIP_HOST_CHECK(up != nullptr, "%s: nothing to do (no target, no up)", name);
+    return 0;
+}
+
+// runs the statement with TL = the element type of the low-res maps (low_dt checked by the caller)
+#define EVAL_DISPATCH_LOW(low_dt, ...)      \
+    do {                                    \
+        if ((low_dt) == DCLIP_F32) {        \
+            using TL = float;               \
+            __VA_ARGS__;                    \
+        } else if ((low_dt) == DCLIP_BF16) { \
+            using TL = bf16;                \
+            __VA_ARGS__;                    \
+        } else {                            \
+            using TL = f16;                 \
+            __VA_ARGS__;                    \
+        }                                   \
+    } while (0)
 
 }  // namespace

@@ -17,8 +17,9 @@
 // softmax over the classes of each view's resized logits (mmseg's).
 //
 // The view table travels by value in the kernel arguments (no device-side table, no copy), so a
-// launch can be captured in a graph.  Tiling, per-workgroup records, f64 partials and the
-// one-workgroup folds are headeval's (eval_tile.h): no global atomics, no float atomics, the grid
+// launch can be captured in a graph.  Tiling, the scoring epilogue (seg_score, DepthSums), per-workgroup
+// records, f64 partials and the one-workgroup folds are eval_tile.h's, as in headeval.hip; this file
+// keeps the loop over the views and the scaling by 1/V: no global atomics, no float atomics, the grid
 // a function of the shapes alone, two runs bitwise equal.  LDS is sized for the largest view's
 // patch; TW drops from 128 to 64 when any view's patch of a 128-wide tile passes 48 KiB.
 #include "eval_tile.h"
@@ -54,10 +55,7 @@ Tiling make_tiling(int B, int K, ViewTable& vt, int H, int W) {
         t.tw = 64;
     }
     t.nrow = t.ncol = 0;  // per view, in the table
-    t.tiles_x = (W + t.tw - 1) / t.tw;
-    t.tiles_y = (H + TH - 1) / TH;
-    t.ntiles = B * t.tiles_y * t.tiles_x;  // < 2^31: B * H * W is
-    t.nwg = t.ntiles < NWG_MAX ? t.ntiles : NWG_MAX;
+    finish_tiling(t, B, H, W);
     return t;
 }
 
@@ -95,13 +93,10 @@ __global__ __launch_bounds__(256) void ensemble_seg_kernel(ViewTable vt, int H, 
     const int xs = tl.tw >> 2;  // threads along x
     const int tx = tid % xs, ty = tid / xs;
     const float inv_v = 1.f / (float)vt.n;
-    if constexpr (LAB) {
-        for (int e = tid; e < K * K + 1; e += blockDim.x) hist_s[e] = 0u;
-    }
+    if constexpr (LAB) hist_clear<K>(hist_s);
     double lsum = 0.0;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const int b = tile / (tl.tiles_x * tl.tiles_y);
-        const int y0 = ((tile / tl.tiles_x) % tl.tiles_y) * TH, x0 = (tile % tl.tiles_x) * tl.tw;
+        const auto [b, y0, x0] = tile_origin(tile, tl);
         const int y = y0 + ty, x = x0 + 4 * tx;
         const bool active = y < H && x < W;  // every thread stages every view's patch
         float v[4][K];
@@ -112,7 +107,7 @@ __global__ __launch_bounds__(256) void ensemble_seg_kernel(ViewTable vt, int H, 
         for (int iv = 0; iv < vt.n; ++iv) {
             const View vw = vt.v[iv];
             const TileGeom g = view_geom(b, y0, x0, tl.tw, vw, H, W);
-            __syncthreads();  // the previous patch's readers are done (and hist_s is cleared)
+            __syncthreads();  // the previous patch's readers are done
             stage_patch(low_s, (const TL*)vw.low, b, K, vw.h, vw.w, g.ilo, g.nr, g.jlo, g.nc, vw.nrow, vw.ncol);
             __syncthreads();
             if (!active) continue;
@@ -176,72 +171,15 @@ __global__ __launch_bounds__(256) void ensemble_seg_kernel(ViewTable vt, int H, 
         const int64_t pix = ((int64_t)b * H + y) * W + x;
         int t[4] = {-1, -1, -1, -1};
         if constexpr (LAB) load_labels4(lab, lab_dt, pix, n, vec_lab != 0, t);
-        int am[4];
-        int cell_prev = -1;
-        unsigned run = 0;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
+        for (int p = 0; p < 4; ++p)
 #pragma unroll
             for (int k = 0; k < K; ++k) v[p][k] *= inv_v;
-            // argmax: the lowest class index among equal maxima (torch.argmax)
-            float m = v[p][0];
-            int a = 0;
-#pragma unroll
-            for (int k = 1; k < K; ++k)
-                if (v[p][k] > m) {
-                    m = v[p][k];
-                    a = k;
-                }
-            am[p] = a;
-            if constexpr (LAB) {
-                const int tp = t[p];
-                const bool valid = p < n && tp != ignore && tp >= 0 && tp < K;
-                if (valid) {
-                    float vtgt = 0.f, s = 0.f;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        vtgt = k == tp ? v[p][k] : vtgt;
-                        if constexpr (!PROBS) s += __expf(v[p][k] - m);
-                    }
-                    if constexpr (PROBS) lsum += (double)(-__logf(vtgt));  // -log(mean prob[t])
-                    else lsum += (double)(__logf(s) - (vtgt - m));         // -log softmax(mean)[t]
-                }
-                // runs of equal (target, prediction) cells among the four pixels: one LDS add each
-                const int cell = valid ? tp * K + a : -1;
-                if (cell != cell_prev) {
-                    if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
-                    cell_prev = cell;
-                    run = 0;
-                }
-                ++run;
-            }
-        }
-        if constexpr (LAB) {
-            if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
-        }
-        if (pred != nullptr) {
-            if (vec_pred) {
-                *(uint32_t*)(pred + pix) = (uint32_t)am[0] | ((uint32_t)am[1] << 8) | ((uint32_t)am[2] << 16) |
-                                           ((uint32_t)am[3] << 24);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    if (p < n) pred[pix + p] = (uint8_t)am[p];
-            }
-        }
+        int am[4];
+        seg_score<K, 4, LAB, PROBS>(v, t, n, ignore, hist_s, lsum, am);
+        store_pred4(pred, pix, n, vec_pred != 0, am);
     }
-    if constexpr (LAB) {
-        char* rec = ws + (int64_t)blockIdx.x * record_bytes(K);
-        double a[1] = {lsum};
-        wg_partials<1>(a, red_s, (double*)rec);  // __syncthreads inside: every LDS add has landed after it
-        unsigned* hist = (unsigned*)(rec + NSUM * 8);
-        if (tid == 0) {
-            unsigned c = 0;
-            for (int e = 0; e < K * K; ++e) c += hist_s[e];
-            hist[K * K] = c;  // #valid
-        }
-        for (int e = tid; e < K * K; e += blockDim.x) hist[e] = hist_s[e];
-    }
+    if constexpr (LAB) seg_flush<K>(hist_s, lsum, red_s, ws);
 }
 
 // ----------------------------------------------------------------------------- depth
@@ -258,12 +196,9 @@ __global__ __launch_bounds__(256) void ensemble_depth_kernel(ViewTable vt, int H
     const int xs = tl.tw >> 2;
     const int tx = tid % xs, ty = tid / xs;
     const float inv_v = 1.f / (float)vt.n;
-    // sums[1..4], [9..11] in f64; the counts [0], [5..8] as integers (exact), widened at the end
-    double s_sq = 0.0, s_log = 0.0, s_abs = 0.0, s_sqrel = 0.0, s_msq = 0.0, s_d = 0.0, s_d2 = 0.0;
-    unsigned n_eval = 0, n_a1 = 0, n_a2 = 0, n_a3 = 0, n_mask = 0;
+    DepthSums acc;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const int b = tile / (tl.tiles_x * tl.tiles_y);
-        const int y0 = ((tile / tl.tiles_x) % tl.tiles_y) * TH, x0 = (tile % tl.tiles_x) * tl.tw;
+        const auto [b, y0, x0] = tile_origin(tile, tl);
         const int y = y0 + ty, x = x0 + 4 * tx;
         const bool active = y < H && x < W;
         float u[4] = {0.f, 0.f, 0.f, 0.f};
@@ -308,67 +243,10 @@ __global__ __launch_bounds__(256) void ensemble_depth_kernel(ViewTable vt, int H
         const int64_t pix = ((int64_t)b * H + y) * W + x;
 #pragma unroll
         for (int p = 0; p < 4; ++p) u[p] *= inv_v;
-        if (up != nullptr) {
-            if (vec) {
-                *(float4*)(up + pix) = make_float4(u[0], u[1], u[2], u[3]);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    if (p < n) up[pix + p] = u[p];
-            }
-        }
-        if constexpr (TGT) {
-            float tg[4] = {0.f, 0.f, 0.f, 0.f};
-            bool tm[4];
-            if (vec) {
-                const float4 a = *(const float4*)(gt + pix);
-                tg[0] = a.x; tg[1] = a.y; tg[2] = a.z; tg[3] = a.w;
-                const uint32_t mk = mask ? *(const uint32_t*)(mask + pix) : 0x01010101u;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) tm[p] = ((mk >> (8 * p)) & 0xffu) != 0;
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    tm[p] = false;
-                    if (p < n) {
-                        tg[p] = gt[pix + p];
-                        tm[p] = mask == nullptr || mask[pix + p] != 0;
-                    }
-                }
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                if (!tm[p]) continue;
-                const float gtv = tg[p];
-                // the trainer's masked RMSE (unclamped) and the SILog pass-0 sums, d as dclip_upsample_silog
-                ++n_mask;
-                const float dm = gtv - u[p];
-                s_msq += (double)(dm * dm);
-                const float d = logf(fmaxf(u[p], eps)) - logf(fmaxf(gtv, eps));
-                s_d += (double)d;
-                s_d2 += (double)d * (double)d;
-                // compute_depth_errors: mask && min <= gt <= max, optionally clamped prediction
-                if (!(gtv >= dmin && gtv <= dmax)) continue;
-                const float pr = clamp_pred ? fminf(fmaxf(u[p], dmin), dmax) : u[p];
-                ++n_eval;
-                const float thr = fmaxf(gtv / pr, pr / gtv);
-                n_a1 += thr < 1.25f ? 1u : 0u;
-                n_a2 += thr < 1.5625f ? 1u : 0u;
-                n_a3 += thr < 1.953125f ? 1u : 0u;
-                const float df = gtv - pr;
-                const float dl = logf(gtv) - logf(pr);
-                s_sq += (double)(df * df);
-                s_log += (double)(dl * dl);
-                s_abs += (double)(fabsf(df) / gtv);
-                s_sqrel += (double)(df * df / gtv);
-            }
-        }
+        store_up4(up, pix, n, vec != 0, u);
+        if constexpr (TGT) acc.score4(u, gt, mask, pix, n, vec != 0, dmin, dmax, clamp_pred, eps);
     }
-    if constexpr (TGT) {
-        double a[NSUM] = {(double)n_eval, s_sq,          s_log,          s_abs, s_sqrel, (double)n_a1,
-                          (double)n_a2,   (double)n_a3, (double)n_mask, s_msq, s_d,     s_d2};
-        wg_partials<NSUM>(a, red_s, (double*)(ws + (int64_t)blockIdx.x * record_bytes(1)));
-    }
+    if constexpr (TGT) acc.flush(red_s, ws);
 }
 
 template <typename TL, bool PROBS>
@@ -377,9 +255,7 @@ void launch_seg(ViewTable& vt, int B, int H, int W, const void* lab, int lab_dt,
     constexpr int K = 19;
     const Tiling tl = make_tiling(B, K, vt, H, W);
     const int nth = (tl.tw / 4) * TH;
-    const int lab_align = lab_dt == 0 ? 16 : lab_dt == 1 ? 16 : 4;
-    const int vec_lab = lab != nullptr && W % 4 == 0 && (uintptr_t)lab % lab_align == 0;
-    const int vec_pred = pred != nullptr && W % 4 == 0 && (uintptr_t)pred % 4 == 0;
+    const int vec_lab = labels_aligned(lab, lab_dt, W), vec_pred = pred_aligned(pred, W);
     if (lab != nullptr) {
         ensemble_seg_kernel<TL, K, true, PROBS><<<tl.nwg, nth, tl.lds, st>>>(vt, H, W, tl, lab, lab_dt, ignore, vec_lab,
                                                                              vec_pred, pred, (char*)ws);
@@ -395,8 +271,7 @@ void launch_depth(ViewTable& vt, int B, int H, int W, const float* gt, const uin
                   int clamp_pred, float eps, float* up, double* sums, void* ws, hipStream_t st) {
     const Tiling tl = make_tiling(B, 1, vt, H, W);
     const int nth = (tl.tw / 4) * TH;
-    const int vec = W % 4 == 0 && (gt == nullptr || (uintptr_t)gt % 16 == 0) &&
-                    (mask == nullptr || (uintptr_t)mask % 4 == 0) && (up == nullptr || (uintptr_t)up % 16 == 0);
+    const int vec = depth_aligned(gt, mask, up, W);
     if (gt != nullptr) {
         ensemble_depth_kernel<TL, true><<<tl.nwg, nth, tl.lds, st>>>(vt, H, W, tl, gt, mask, dmin, dmax, clamp_pred,
                                                                      eps, vec, up, (char*)ws);
@@ -446,27 +321,14 @@ extern "C" int dclip_ensemble_eval_seg(int low_dt, const dclip_view* views, int 
                      "dclip_ensemble_eval_seg: average=%d (0: mean of the logits, 1: mean of the probabilities)",
                      average);
     ENSEMBLE_VIEW_CHECKS("dclip_ensemble_eval_seg");
-    if (labels != nullptr) {
-        DCLIP_HOST_CHECK(lab_dt >= 0 && lab_dt <= 2,
-                         "dclip_ensemble_eval_seg: lab_dt=%d: labels int64 (0), int32 (1) or uint8 (2)", lab_dt);
-        DCLIP_HOST_CHECK(cm && loss_sum && count,
-                         "dclip_ensemble_eval_seg: cm, loss_sum and count required with labels");
+    if (int rc = check_seg_outputs("dclip_ensemble_eval_seg", labels, lab_dt, pred, cm, loss_sum, count)) return rc;
+    if (labels != nullptr)
         DCLIP_HOST_CHECK(ws != nullptr && ((uintptr_t)ws % 8) == 0,
                          "dclip_ensemble_eval_seg: ws=%p (dclip_ensemble_eval_ws_bytes(B, K, nviews) bytes, 8-byte "
                          "aligned) required", ws);
-    } else {
-        DCLIP_HOST_CHECK(!cm && !loss_sum && !count,
-                         "dclip_ensemble_eval_seg: cm, loss_sum and count must be null without labels");
-        DCLIP_HOST_CHECK(pred != nullptr, "dclip_ensemble_eval_seg: nothing to do (no labels, no pred)");
-    }
     hipStream_t st = (hipStream_t)stream;
-#define ENSEMBLE_SEG(TL)                                                                                      \
-    (average ? launch_seg<TL, true>(vt, B, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st) \
-             : launch_seg<TL, false>(vt, B, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st))
-    if (low_dt == DCLIP_F32) ENSEMBLE_SEG(float);
-    else if (low_dt == DCLIP_BF16) ENSEMBLE_SEG(bf16);
-    else ENSEMBLE_SEG(f16);
-#undef ENSEMBLE_SEG
+    EVAL_DISPATCH_LOW(low_dt, (average ? launch_seg<TL, true> : launch_seg<TL, false>)(
+                                  vt, B, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }
@@ -475,21 +337,14 @@ extern "C" int dclip_ensemble_eval_depth(int low_dt, const dclip_view* views, in
                                          const uint8_t* mask, int H, int W, float min_depth, float max_depth,
                                          int clamp_pred, float eps, float* up, double* sums, void* ws, void* stream) {
     ENSEMBLE_VIEW_CHECKS("dclip_ensemble_eval_depth");
-    if (target != nullptr) {
-        DCLIP_HOST_CHECK(sums != nullptr, "dclip_ensemble_eval_depth: sums required with a target");
+    if (int rc = check_depth_outputs("dclip_ensemble_eval_depth", target, sums, up)) return rc;
+    if (target != nullptr)
         DCLIP_HOST_CHECK(ws != nullptr && ((uintptr_t)ws % 8) == 0,
                          "dclip_ensemble_eval_depth: ws=%p (dclip_ensemble_eval_ws_bytes(B, 1, nviews) bytes, 8-byte "
                          "aligned) required", ws);
-    } else {  // prediction only: mask, sums and ws are not touched
-        DCLIP_HOST_CHECK(up != nullptr, "dclip_ensemble_eval_depth: nothing to do (no target, no up)");
-    }
     hipStream_t st = (hipStream_t)stream;
-    if (low_dt == DCLIP_F32)
-        launch_depth<float>(vt, B, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else if (low_dt == DCLIP_BF16)
-        launch_depth<bf16>(vt, B, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else
-        launch_depth<f16>(vt, B, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
+    EVAL_DISPATCH_LOW(low_dt, launch_depth<TL>(vt, B, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums,
+                                               ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }

@@ -24,6 +24,10 @@
 //   * eval_fold_kernel (one workgroup) adds the workgroups' tiles and partials in workgroup order
 //     into the caller's running cm / loss_sum / count / sums.  The grid is a function of the shapes
 //     alone, so two runs are bitwise equal.
+//
+// This file keeps the single-view tile walk and interpolation; what follows a thread's K values /
+// 4 depths (argmax, CE, confusion counts, the depth terms, the stores and the workgroup's record)
+// is eval_tile.h's scoring epilogue, shared with headensemble / headslide / headslidetta.hip.
 #include "eval_tile.h"
 
 namespace {
@@ -38,10 +42,7 @@ Tiling make_tiling(int B, int K, int h, int w, int H, int W) {
         t.ncol = low_span(t.tw, w, W);
     }
     t.lds = (size_t)K * t.nrow * t.ncol * 4;
-    t.tiles_x = (W + t.tw - 1) / t.tw;
-    t.tiles_y = (H + TH - 1) / TH;
-    t.ntiles = B * t.tiles_y * t.tiles_x;  // < 2^31: B * H * W is
-    t.nwg = t.ntiles < NWG_MAX ? t.ntiles : NWG_MAX;
+    finish_tiling(t, B, H, W);
     return t;
 }
 
@@ -58,13 +59,11 @@ __global__ __launch_bounds__(256) void eval_seg_kernel(const TL* __restrict__ lo
     const int tid = threadIdx.x;
     const int xs = tl.tw >> 2;  // threads along x
     const int tx = tid % xs, ty = tid / xs;
-    if constexpr (LAB) {
-        for (int e = tid; e < K * K + 1; e += blockDim.x) hist_s[e] = 0u;
-    }
+    if constexpr (LAB) hist_clear<K>(hist_s);
     double lsum = 0.0;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const TileGeom g = tile_geom(tile, tl.tiles_x, tl.tiles_y, tl.tw, h, w, H, W, tl.nrow, tl.ncol);
-        __syncthreads();  // the previous tile's readers are done (and hist_s is cleared)
+        const TileGeom g = tile_geom(tile, tl, h, w, H, W);
+        __syncthreads();  // the previous tile's readers are done
         stage_patch(low_s, low, g.b, K, h, w, g.ilo, g.nr, g.jlo, g.nc, tl.nrow, tl.ncol);
         __syncthreads();
         const int y = g.y0 + ty, x = g.x0 + 4 * tx;
@@ -107,70 +106,11 @@ __global__ __launch_bounds__(256) void eval_seg_kernel(const TL* __restrict__ lo
             }
         }
         int am[4];
-        int cell_prev = -1;
-        unsigned run = 0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            // argmax: the lowest class index among equal maxima (torch.argmax)
-            float m = v[p][0];
-            int a = 0;
-#pragma unroll
-            for (int k = 1; k < K; ++k)
-                if (v[p][k] > m) {
-                    m = v[p][k];
-                    a = k;
-                }
-            am[p] = a;
-            if constexpr (LAB) {
-                const int tp = t[p];
-                const bool valid = p < n && tp != ignore && tp >= 0 && tp < K;
-                if (valid) {
-                    float vt = 0.f, s = 0.f;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        vt = k == tp ? v[p][k] : vt;
-                        s += __expf(v[p][k] - m);
-                    }
-                    lsum += (double)(__logf(s) - (vt - m));  // -log softmax[t], as dclip_upsample_ce
-                }
-                // runs of equal (target, prediction) cells among the four pixels: one LDS add each
-                const int cell = valid ? tp * K + a : -1;
-                if (cell != cell_prev) {
-                    if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
-                    cell_prev = cell;
-                    run = 0;
-                }
-                ++run;
-            }
-        }
-        if constexpr (LAB) {
-            if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
-        }
-        if (pred != nullptr) {
-            if (vec_pred) {
-                *(uint32_t*)(pred + pix) = (uint32_t)am[0] | ((uint32_t)am[1] << 8) | ((uint32_t)am[2] << 16) |
-                                           ((uint32_t)am[3] << 24);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    if (p < n) pred[pix + p] = (uint8_t)am[p];
-            }
-        }
+        seg_score<K, 4, LAB, false>(v, t, n, ignore, hist_s, lsum, am);
+        store_pred4(pred, pix, n, vec_pred != 0, am);
     }
-    if constexpr (LAB) {
-        char* rec = ws + (int64_t)blockIdx.x * record_bytes(K);
-        double a[1] = {lsum};
-        wg_partials<1>(a, red_s, (double*)rec);  // __syncthreads inside: every LDS add has landed after it
-        unsigned* hist = (unsigned*)(rec + NSUM * 8);
-        if (tid == 0) {
-            unsigned c = 0;
-            for (int e = 0; e < K * K; ++e) c += hist_s[e];
-            hist[K * K] = c;  // #valid
-        }
-        for (int e = tid; e < K * K; e += blockDim.x) hist[e] = hist_s[e];
-    }
+    if constexpr (LAB) seg_flush<K>(hist_s, lsum, red_s, ws);
 }
-
 
 // ----------------------------------------------------------------------------- depth
 template <typename TL>
@@ -184,11 +124,9 @@ __global__ __launch_bounds__(256) void eval_depth_kernel(const TL* __restrict__ 
     const int tid = threadIdx.x;
     const int xs = tl.tw >> 2;
     const int tx = tid % xs, ty = tid / xs;
-    // sums[1..4], [9..11] in f64; the counts [0], [5..8] as integers (exact), widened at the end
-    double s_sq = 0.0, s_log = 0.0, s_abs = 0.0, s_sqrel = 0.0, s_msq = 0.0, s_d = 0.0, s_d2 = 0.0;
-    unsigned n_eval = 0, n_a1 = 0, n_a2 = 0, n_a3 = 0, n_mask = 0;
+    DepthSums acc;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const TileGeom g = tile_geom(tile, tl.tiles_x, tl.tiles_y, tl.tw, h, w, H, W, tl.nrow, tl.ncol);
+        const TileGeom g = tile_geom(tile, tl, h, w, H, W);
         __syncthreads();
         stage_patch(low_s, low, g.b, 1, h, w, g.ilo, g.nr, g.jlo, g.nc, tl.nrow, tl.ncol);
         __syncthreads();
@@ -196,24 +134,6 @@ __global__ __launch_bounds__(256) void eval_depth_kernel(const TL* __restrict__ 
         if (y >= H || x >= W) continue;
         const int n = W - x < 4 ? W - x : 4;
         const int64_t pix = ((int64_t)g.b * H + y) * W + x;
-        float tg[4] = {0.f, 0.f, 0.f, 0.f};
-        bool tm[4];
-        if (vec) {
-            const float4 a = *(const float4*)(gt + pix);
-            tg[0] = a.x; tg[1] = a.y; tg[2] = a.z; tg[3] = a.w;
-            const uint32_t mk = mask ? *(const uint32_t*)(mask + pix) : 0x01010101u;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) tm[p] = ((mk >> (8 * p)) & 0xffu) != 0;
-        } else {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                tm[p] = false;
-                if (p < n) {
-                    tg[p] = gt[pix + p];
-                    tm[p] = mask == nullptr || mask[pix + p] != 0;
-                }
-            }
-        }
         const Lerp Y = lerp_index(y, h, H);
         int r0 = Y.i0 - g.ilo, r1 = Y.i1 - g.ilo;
         r0 = r0 < g.nr ? r0 : g.nr - 1;
@@ -227,49 +147,13 @@ __global__ __launch_bounds__(256) void eval_depth_kernel(const TL* __restrict__ 
             int c0 = X.i0 - g.jlo, c1 = X.i1 - g.jlo;
             c0 = c0 < g.nc ? c0 : g.nc - 1;
             c1 = c1 < g.nc ? c1 : g.nc - 1;
-            u[p] = Y.l0 * (X.l0 * top[c0] + X.l1 * top[c1]) + Y.l1 * (X.l0 * bot[c0] + X.l1 * bot[c1]);
+            u[p] = bilerp_depth(p, Y.l0, Y.l1, X.l0, X.l1, top[c0], top[c1], bot[c0], bot[c1]);  // slot = column % 4
         }
-        if (up != nullptr) {
-            if (vec) {
-                *(float4*)(up + pix) = make_float4(u[0], u[1], u[2], u[3]);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    if (p < n) up[pix + p] = u[p];
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            if (!tm[p]) continue;
-            const float gtv = tg[p];
-            // the trainer's masked RMSE (unclamped) and the SILog pass-0 sums, d as dclip_upsample_silog
-            ++n_mask;
-            const float dm = gtv - u[p];
-            s_msq += (double)(dm * dm);
-            const float d = logf(fmaxf(u[p], eps)) - logf(fmaxf(gtv, eps));
-            s_d += (double)d;
-            s_d2 += (double)d * (double)d;
-            // compute_depth_errors: mask && min <= gt <= max, optionally clamped prediction
-            if (!(gtv >= dmin && gtv <= dmax)) continue;
-            const float pr = clamp_pred ? fminf(fmaxf(u[p], dmin), dmax) : u[p];
-            ++n_eval;
-            const float thr = fmaxf(gtv / pr, pr / gtv);
-            n_a1 += thr < 1.25f ? 1u : 0u;
-            n_a2 += thr < 1.5625f ? 1u : 0u;
-            n_a3 += thr < 1.953125f ? 1u : 0u;
-            const float df = gtv - pr;
-            const float dl = logf(gtv) - logf(pr);
-            s_sq += (double)(df * df);
-            s_log += (double)(dl * dl);
-            s_abs += (double)(fabsf(df) / gtv);
-            s_sqrel += (double)(df * df / gtv);
-        }
+        store_up4(up, pix, n, vec != 0, u);
+        acc.score4(u, gt, mask, pix, n, vec != 0, dmin, dmax, clamp_pred, eps);
     }
-    double a[NSUM] = {(double)n_eval, s_sq,          s_log,          s_abs, s_sqrel, (double)n_a1,
-                      (double)n_a2,   (double)n_a3, (double)n_mask, s_msq, s_d,     s_d2};
-    wg_partials<NSUM>(a, red_s, (double*)(ws + (int64_t)blockIdx.x * record_bytes(1)));
+    acc.flush(red_s, ws);
 }
-
 
 template <typename TL>
 void launch_seg(const void* low, int B, int h, int w, int H, int W, const void* lab, int lab_dt, int ignore,
@@ -277,9 +161,7 @@ void launch_seg(const void* low, int B, int h, int w, int H, int W, const void* 
     constexpr int K = 19;
     const Tiling tl = make_tiling(B, K, h, w, H, W);
     const int nth = (tl.tw / 4) * TH;
-    const int lab_align = lab_dt == 0 ? 16 : lab_dt == 1 ? 16 : 4;
-    const int vec_lab = lab != nullptr && W % 4 == 0 && (uintptr_t)lab % lab_align == 0;
-    const int vec_pred = pred != nullptr && W % 4 == 0 && (uintptr_t)pred % 4 == 0;
+    const int vec_lab = labels_aligned(lab, lab_dt, W), vec_pred = pred_aligned(pred, W);
     if (lab != nullptr) {
         eval_seg_kernel<TL, K, true><<<tl.nwg, nth, tl.lds, st>>>((const TL*)low, h, w, H, W, tl, lab, lab_dt, ignore,
                                                                   vec_lab, vec_pred, pred, (char*)ws);
@@ -296,8 +178,7 @@ void launch_depth(const void* low, int B, int h, int w, int H, int W, const floa
                   hipStream_t st) {
     const Tiling tl = make_tiling(B, 1, h, w, H, W);
     const int nth = (tl.tw / 4) * TH;
-    const int vec = W % 4 == 0 && (uintptr_t)gt % 16 == 0 && (mask == nullptr || (uintptr_t)mask % 4 == 0) &&
-                    (up == nullptr || (uintptr_t)up % 16 == 0);
+    const int vec = depth_aligned(gt, mask, up, W);
     eval_depth_kernel<TL><<<tl.nwg, nth, tl.lds, st>>>((const TL*)low, h, w, H, W, tl, gt, mask, dmin, dmax,
                                                        clamp_pred, eps, vec, up, (char*)ws);
     eval_depth_fold_kernel<<<1, 256, 0, st>>>((const char*)ws, tl.nwg, sums);
@@ -326,25 +207,14 @@ extern "C" int dclip_upsample_eval_seg(int low_dt, const void* logits, int B, in
     DCLIP_HOST_CHECK(K == 19, "dclip_upsample_eval_seg: K=%d (built for the 19 Cityscapes classes)", K);
     EVAL_SIZE_CHECKS("dclip_upsample_eval_seg");
     DCLIP_HOST_CHECK(logits != nullptr, "dclip_upsample_eval_seg: logits required");
-    if (labels != nullptr) {
-        DCLIP_HOST_CHECK(lab_dt >= 0 && lab_dt <= 2,
-                         "dclip_upsample_eval_seg: lab_dt=%d: labels int64 (0), int32 (1) or uint8 (2)", lab_dt);
-        DCLIP_HOST_CHECK(cm && loss_sum && count, "dclip_upsample_eval_seg: cm, loss_sum and count required with labels");
+    if (int rc = check_seg_outputs("dclip_upsample_eval_seg", labels, lab_dt, pred, cm, loss_sum, count)) return rc;
+    if (labels != nullptr)
         DCLIP_HOST_CHECK(ws != nullptr && ((uintptr_t)ws % 8) == 0,
                          "dclip_upsample_eval_seg: ws (dclip_upsample_eval_ws_bytes(B, K, h, w) bytes, 8-byte aligned) "
                          "required");
-    } else {
-        DCLIP_HOST_CHECK(!cm && !loss_sum && !count,
-                         "dclip_upsample_eval_seg: cm, loss_sum and count must be null without labels");
-        DCLIP_HOST_CHECK(pred != nullptr, "dclip_upsample_eval_seg: nothing to do (no labels, no pred)");
-    }
     hipStream_t st = (hipStream_t)stream;
-    if (low_dt == DCLIP_F32)
-        launch_seg<float>(logits, B, h, w, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st);
-    else if (low_dt == DCLIP_BF16)
-        launch_seg<bf16>(logits, B, h, w, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st);
-    else
-        launch_seg<f16>(logits, B, h, w, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st);
+    EVAL_DISPATCH_LOW(low_dt, launch_seg<TL>(logits, B, h, w, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum,
+                                             count, ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }
@@ -358,12 +228,8 @@ extern "C" int dclip_upsample_eval_depth(int low_dt, const void* pred, int B, in
                      "dclip_upsample_eval_depth: ws (dclip_upsample_eval_ws_bytes(B, 1, h, w) bytes, 8-byte aligned) "
                      "required");
     hipStream_t st = (hipStream_t)stream;
-    if (low_dt == DCLIP_F32)
-        launch_depth<float>(pred, B, h, w, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else if (low_dt == DCLIP_BF16)
-        launch_depth<bf16>(pred, B, h, w, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else
-        launch_depth<f16>(pred, B, h, w, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
+    EVAL_DISPATCH_LOW(low_dt, launch_depth<TL>(pred, B, h, w, H, W, target, mask, min_depth, max_depth, clamp_pred, eps,
+                                               up, sums, ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }

@@ -13,10 +13,11 @@
 // All windows have one size (wh x ww at the output, h x w low-res), so the LDS patch has one size.
 // The window table travels by value in the kernel arguments (no device-side table, no copy), so a
 // launch can be captured in a graph.  Whether a tile skips a window depends on the tile alone:
-// every thread of the workgroup reaches every barrier.  Tiling, per-workgroup records, f64
-// partials and the one-workgroup folds are headeval's (eval_tile.h): no global atomics, no float
-// atomics, the grid a function of the shapes alone, two runs bitwise equal.  TW drops from 128 to
-// 64 when the patch of a 128-wide tile passes 48 KiB.
+// every thread of the workgroup reaches every barrier.  Tiling, the scoring epilogue (seg_score,
+// DepthSums), per-workgroup records, f64 partials and the one-workgroup folds are eval_tile.h's, as
+// in headeval.hip; this file keeps the loop over the windows and the division by the count: no
+// global atomics, no float atomics, the grid a function of the shapes alone, two runs bitwise
+// equal.  TW drops from 128 to 64 when the patch of a 128-wide tile passes 48 KiB.
 #include "eval_tile.h"
 
 namespace {
@@ -42,10 +43,7 @@ Tiling make_tiling(int B, int K, const WinShape& s) {
         if (t.lds <= (size_t)LDS_TILE_MAX) break;
         t.tw = 64;
     }
-    t.tiles_x = (s.W + t.tw - 1) / t.tw;
-    t.tiles_y = (s.H + TH - 1) / TH;
-    t.ntiles = B * t.tiles_y * t.tiles_x;  // < 2^31: B * H * W is
-    t.nwg = t.ntiles < NWG_MAX ? t.ntiles : NWG_MAX;
+    finish_tiling(t, B, s.H, s.W);
     return t;
 }
 
@@ -84,14 +82,10 @@ __global__ __launch_bounds__(256) void slide_seg_kernel(WinTable wt, WinShape s,
     const int xs = tl.tw >> 2;  // threads along x
     const int tx = tid % xs, ty = tid / xs;
     const int H = s.H, W = s.W;
-    if constexpr (LAB) {
-        for (int e = tid; e < K * K + 1; e += blockDim.x) hist_s[e] = 0u;
-        __syncthreads();
-    }
+    if constexpr (LAB) hist_clear<K>(hist_s);
     double lsum = 0.0;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const int b = tile / (tl.tiles_x * tl.tiles_y);
-        const int y0 = ((tile / tl.tiles_x) % tl.tiles_y) * TH, x0 = (tile % tl.tiles_x) * tl.tw;
+        const auto [b, y0, x0] = tile_origin(tile, tl);
         const int y = y0 + ty, x = x0 + 4 * tx;
         const bool active = y < H && x < W;  // every thread stages every patch
         float v[4][K];
@@ -150,74 +144,18 @@ __global__ __launch_bounds__(256) void slide_seg_kernel(WinTable wt, WinShape s,
         const int64_t pix = ((int64_t)b * H + y) * W + x;
         int t[4] = {-1, -1, -1, -1};
         if constexpr (LAB) load_labels4(lab, lab_dt, pix, n, vec_lab != 0, t);
-        int am[4];
-        int cell_prev = -1;
-        unsigned run = 0;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
+        for (int p = 0; p < 4; ++p)
             if (cnt[p] > 1) {  // x / 1 is x
                 const float c = (float)cnt[p];
 #pragma unroll
                 for (int k = 0; k < K; ++k) v[p][k] = div_rounded(v[p][k], c);
             }
-            // argmax: the lowest class index among equal maxima (torch.argmax)
-            float m = v[p][0];
-            int a = 0;
-#pragma unroll
-            for (int k = 1; k < K; ++k)
-                if (v[p][k] > m) {
-                    m = v[p][k];
-                    a = k;
-                }
-            am[p] = a;
-            if constexpr (LAB) {
-                const int tp = t[p];
-                const bool valid = p < n && tp != ignore && tp >= 0 && tp < K;
-                if (valid) {
-                    float vtgt = 0.f, sum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        vtgt = k == tp ? v[p][k] : vtgt;
-                        sum += __expf(v[p][k] - m);
-                    }
-                    lsum += (double)(__logf(sum) - (vtgt - m));  // -log softmax(result)[t]
-                }
-                // runs of equal (target, prediction) cells among the four pixels: one LDS add each
-                const int cell = valid ? tp * K + a : -1;
-                if (cell != cell_prev) {
-                    if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
-                    cell_prev = cell;
-                    run = 0;
-                }
-                ++run;
-            }
-        }
-        if constexpr (LAB) {
-            if (cell_prev >= 0) atomicAdd(&hist_s[cell_prev], run);
-        }
-        if (pred != nullptr) {
-            if (vec_pred) {
-                *(uint32_t*)(pred + pix) = (uint32_t)am[0] | ((uint32_t)am[1] << 8) | ((uint32_t)am[2] << 16) |
-                                           ((uint32_t)am[3] << 24);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    if (p < n) pred[pix + p] = (uint8_t)am[p];
-            }
-        }
+        int am[4];
+        seg_score<K, 4, LAB, false>(v, t, n, ignore, hist_s, lsum, am);
+        store_pred4(pred, pix, n, vec_pred != 0, am);
     }
-    if constexpr (LAB) {
-        char* rec = ws + (int64_t)blockIdx.x * record_bytes(K);
-        double a[1] = {lsum};
-        wg_partials<1>(a, red_s, (double*)rec);  // __syncthreads inside: every LDS add has landed after it
-        unsigned* hist = (unsigned*)(rec + NSUM * 8);
-        if (tid == 0) {
-            unsigned c = 0;
-            for (int e = 0; e < K * K; ++e) c += hist_s[e];
-            hist[K * K] = c;  // #valid
-        }
-        for (int e = tid; e < K * K; e += blockDim.x) hist[e] = hist_s[e];
-    }
+    if constexpr (LAB) seg_flush<K>(hist_s, lsum, red_s, ws);
 }
 
 // ----------------------------------------------------------------------------- depth
@@ -234,12 +172,9 @@ __global__ __launch_bounds__(256) void slide_depth_kernel(WinTable wt, WinShape 
     const int xs = tl.tw >> 2;
     const int tx = tid % xs, ty = tid / xs;
     const int H = s.H, W = s.W;
-    // sums[1..4], [9..11] in f64; the counts [0], [5..8] as integers (exact), widened at the end
-    double s_sq = 0.0, s_log = 0.0, s_abs = 0.0, s_sqrel = 0.0, s_msq = 0.0, s_d = 0.0, s_d2 = 0.0;
-    unsigned n_eval = 0, n_a1 = 0, n_a2 = 0, n_a3 = 0, n_mask = 0;
+    DepthSums acc;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const int b = tile / (tl.tiles_x * tl.tiles_y);
-        const int y0 = ((tile / tl.tiles_x) % tl.tiles_y) * TH, x0 = (tile % tl.tiles_x) * tl.tw;
+        const auto [b, y0, x0] = tile_origin(tile, tl);
         const int y = y0 + ty, x = x0 + 4 * tx;
         const bool active = y < H && x < W;
         float u[4] = {0.f, 0.f, 0.f, 0.f};
@@ -287,67 +222,10 @@ __global__ __launch_bounds__(256) void slide_depth_kernel(WinTable wt, WinShape 
 #pragma unroll
         for (int p = 0; p < 4; ++p)
             if (cnt[p] > 1) u[p] = div_rounded(u[p], (float)cnt[p]);
-        if (up != nullptr) {
-            if (vec) {
-                *(float4*)(up + pix) = make_float4(u[0], u[1], u[2], u[3]);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    if (p < n) up[pix + p] = u[p];
-            }
-        }
-        if constexpr (TGT) {
-            float tg[4] = {0.f, 0.f, 0.f, 0.f};
-            bool tm[4];
-            if (vec) {
-                const float4 a = *(const float4*)(gt + pix);
-                tg[0] = a.x; tg[1] = a.y; tg[2] = a.z; tg[3] = a.w;
-                const uint32_t mk = mask ? *(const uint32_t*)(mask + pix) : 0x01010101u;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) tm[p] = ((mk >> (8 * p)) & 0xffu) != 0;
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    tm[p] = false;
-                    if (p < n) {
-                        tg[p] = gt[pix + p];
-                        tm[p] = mask == nullptr || mask[pix + p] != 0;
-                    }
-                }
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                if (!tm[p]) continue;
-                const float gtv = tg[p];
-                // the trainer's masked RMSE (unclamped) and the SILog pass-0 sums, d as dclip_upsample_silog
-                ++n_mask;
-                const float dm = gtv - u[p];
-                s_msq += (double)(dm * dm);
-                const float d = logf(fmaxf(u[p], eps)) - logf(fmaxf(gtv, eps));
-                s_d += (double)d;
-                s_d2 += (double)d * (double)d;
-                // compute_depth_errors: mask && min <= gt <= max, optionally clamped prediction
-                if (!(gtv >= dmin && gtv <= dmax)) continue;
-                const float pr = clamp_pred ? fminf(fmaxf(u[p], dmin), dmax) : u[p];
-                ++n_eval;
-                const float thr = fmaxf(gtv / pr, pr / gtv);
-                n_a1 += thr < 1.25f ? 1u : 0u;
-                n_a2 += thr < 1.5625f ? 1u : 0u;
-                n_a3 += thr < 1.953125f ? 1u : 0u;
-                const float df = gtv - pr;
-                const float dl = logf(gtv) - logf(pr);
-                s_sq += (double)(df * df);
-                s_log += (double)(dl * dl);
-                s_abs += (double)(fabsf(df) / gtv);
-                s_sqrel += (double)(df * df / gtv);
-            }
-        }
+        store_up4(up, pix, n, vec != 0, u);
+        if constexpr (TGT) acc.score4(u, gt, mask, pix, n, vec != 0, dmin, dmax, clamp_pred, eps);
     }
-    if constexpr (TGT) {
-        double a[NSUM] = {(double)n_eval, s_sq,          s_log,          s_abs, s_sqrel, (double)n_a1,
-                          (double)n_a2,   (double)n_a3, (double)n_mask, s_msq, s_d,     s_d2};
-        wg_partials<NSUM>(a, red_s, (double*)(ws + (int64_t)blockIdx.x * record_bytes(1)));
-    }
+    if constexpr (TGT) acc.flush(red_s, ws);
 }
 
 template <typename TL>
@@ -356,9 +234,7 @@ void launch_seg(const WinTable& wt, const WinShape& s, int B, const void* lab, i
     constexpr int K = 19;
     const Tiling tl = make_tiling(B, K, s);
     const int nth = (tl.tw / 4) * TH;
-    const int lab_align = lab_dt == 0 ? 16 : lab_dt == 1 ? 16 : 4;
-    const int vec_lab = lab != nullptr && s.W % 4 == 0 && (uintptr_t)lab % lab_align == 0;
-    const int vec_pred = pred != nullptr && s.W % 4 == 0 && (uintptr_t)pred % 4 == 0;
+    const int vec_lab = labels_aligned(lab, lab_dt, s.W), vec_pred = pred_aligned(pred, s.W);
     if (lab != nullptr) {
         slide_seg_kernel<TL, K, true><<<tl.nwg, nth, tl.lds, st>>>(wt, s, tl, lab, lab_dt, ignore, vec_lab, vec_pred,
                                                                    pred, (char*)ws);
@@ -374,8 +250,7 @@ void launch_depth(const WinTable& wt, const WinShape& s, int B, const float* gt,
                   float dmax, int clamp_pred, float eps, float* up, double* sums, void* ws, hipStream_t st) {
     const Tiling tl = make_tiling(B, 1, s);
     const int nth = (tl.tw / 4) * TH;
-    const int vec = s.W % 4 == 0 && (gt == nullptr || (uintptr_t)gt % 16 == 0) &&
-                    (mask == nullptr || (uintptr_t)mask % 4 == 0) && (up == nullptr || (uintptr_t)up % 16 == 0);
+    const int vec = depth_aligned(gt, mask, up, s.W);
     if (gt != nullptr) {
         slide_depth_kernel<TL, true><<<tl.nwg, nth, tl.lds, st>>>(wt, s, tl, gt, mask, dmin, dmax, clamp_pred, eps, vec,
                                                                   up, (char*)ws);
@@ -386,6 +261,37 @@ void launch_depth(const WinTable& wt, const WinShape& s, int B, const float* gt,
     }
 }
 
+// The checks shared by both entry points; fills the kernel's window table and shape.
+int check_windows(const char* name, int low_dt, const dclip_window* wins, int nwin, int B, int h, int w, int wh, int ww,
+                  int H, int W, WinTable& wt, WinShape& shape) {
+    DCLIP_HOST_CHECK(nwin >= 1 && nwin <= MAXW, "%s: nwin=%d (1 .. %d windows)", name, nwin, MAXW);
+    DCLIP_HOST_CHECK(wins != nullptr, "%s: wins required", name);
+    DCLIP_HOST_CHECK(B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "%s: bad sizes (B=%d, h=%d, w=%d, H=%d, W=%d)", name, B,
+                     h, w, H, W);
+    DCLIP_HOST_CHECK(low_dt == DCLIP_F32 || low_dt == DCLIP_F16 || low_dt == DCLIP_BF16,
+                     "%s: low_dt=%d (f32, f16 or bf16)", name, low_dt);
+    DCLIP_HOST_CHECK(h <= wh && wh <= H, "%s: h=%d <= wh=%d <= H=%d required (window rows)", name, h, wh, H);
+    DCLIP_HOST_CHECK(w <= ww && ww <= W, "%s: w=%d <= ww=%d <= W=%d required (window columns)", name, w, ww, W);
+    DCLIP_HOST_CHECK((int64_t)B * H * W < ((int64_t)1 << 31), "%s: B*H*W = %lld pixels (must be below 2^31)", name,
+                     (long long)((int64_t)B * H * W));
+    wt.n = nwin;
+    for (int i = 0; i < MAXW; ++i) wt.v[i] = dclip_window{nullptr, 0, 0};
+    for (int i = 0; i < nwin; ++i) {
+        const dclip_window& v = wins[i];
+        DCLIP_HOST_CHECK(v.low != nullptr, "%s: window %d: low is null", name, i);
+        DCLIP_HOST_CHECK(v.y0 >= 0 && v.y0 <= H - wh, "%s: window %d: y0=%d (0 <= y0, y0 + wh=%d <= H=%d)", name, i, v.y0,
+                         wh, H);
+        DCLIP_HOST_CHECK(v.x0 >= 0 && v.x0 <= W - ww, "%s: window %d: x0=%d (0 <= x0, x0 + ww=%d <= W=%d)", name, i, v.x0,
+                         ww, W);
+        wt.v[i] = v;
+    }
+    int uy = 0, ux = 0;
+    DCLIP_HOST_CHECK(!first_uncovered(wins, nwin, wh, ww, H, W, &uy, &ux), "%s: pixel (y=%d, x=%d) is covered by no window",
+                     name, uy, ux);
+    shape = WinShape{h, w, wh, ww, H, W};
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t dclip_slide_eval_ws_bytes(int B, int K, int nwin) {
@@ -393,62 +299,21 @@ extern "C" int64_t dclip_slide_eval_ws_bytes(int B, int K, int nwin) {
     return (int64_t)NWG_MAX * record_bytes(K);
 }
 
-// the checks shared by both entry points; fills the kernel's window table and shape
-#define SLIDE_WINDOW_CHECKS(NAME)                                                                                   \
-    DCLIP_HOST_CHECK(nwin >= 1 && nwin <= MAXW, NAME ": nwin=%d (1 .. %d windows)", nwin, MAXW);                    \
-    DCLIP_HOST_CHECK(wins != nullptr, NAME ": wins required");                                                      \
-    DCLIP_HOST_CHECK(B > 0 && h > 0 && w > 0 && H > 0 && W > 0, NAME ": bad sizes (B=%d, h=%d, w=%d, H=%d, W=%d)",  \
-                     B, h, w, H, W);                                                                                \
-    DCLIP_HOST_CHECK(low_dt == DCLIP_F32 || low_dt == DCLIP_F16 || low_dt == DCLIP_BF16,                            \
-                     NAME ": low_dt=%d (f32, f16 or bf16)", low_dt);                                                \
-    DCLIP_HOST_CHECK(h <= wh && wh <= H, NAME ": h=%d <= wh=%d <= H=%d required (window rows)", h, wh, H);          \
-    DCLIP_HOST_CHECK(w <= ww && ww <= W, NAME ": w=%d <= ww=%d <= W=%d required (window columns)", w, ww, W);       \
-    DCLIP_HOST_CHECK((int64_t)B * H * W < ((int64_t)1 << 31), NAME ": B*H*W = %lld pixels (must be below 2^31)",     \
-                     (long long)((int64_t)B * H * W));                                                              \
-    WinTable wt;                                                                                                    \
-    wt.n = nwin;                                                                                                    \
-    for (int i = 0; i < MAXW; ++i) wt.v[i] = dclip_window{nullptr, 0, 0};                                           \
-    for (int i = 0; i < nwin; ++i) {                                                                                \
-        const dclip_window& v = wins[i];                                                                            \
-        DCLIP_HOST_CHECK(v.low != nullptr, NAME ": window %d: low is null", i);                                     \
-        DCLIP_HOST_CHECK(v.y0 >= 0 && v.y0 <= H - wh, NAME ": window %d: y0=%d (0 <= y0, y0 + wh=%d <= H=%d)", i,   \
-                         v.y0, wh, H);                                                                              \
-        DCLIP_HOST_CHECK(v.x0 >= 0 && v.x0 <= W - ww, NAME ": window %d: x0=%d (0 <= x0, x0 + ww=%d <= W=%d)", i,   \
-                         v.x0, ww, W);                                                                              \
-        wt.v[i] = v;                                                                                                \
-    }                                                                                                               \
-    {                                                                                                               \
-        int uy = 0, ux = 0;                                                                                         \
-        DCLIP_HOST_CHECK(!first_uncovered(wins, nwin, wh, ww, H, W, &uy, &ux),                                      \
-                         NAME ": pixel (y=%d, x=%d) is covered by no window", uy, ux);                              \
-    }                                                                                                               \
-    const WinShape shape = {h, w, wh, ww, H, W}
-
 extern "C" int dclip_slide_eval_seg(int low_dt, const dclip_window* wins, int nwin, int B, int K, int h, int w, int wh,
                                     int ww, const void* labels, int lab_dt, int H, int W, int ignore_index,
                                     uint8_t* pred, int64_t* cm, double* loss_sum, unsigned long long* count, void* ws,
                                     void* stream) {
     DCLIP_HOST_CHECK(K == 19, "dclip_slide_eval_seg: K=%d (built for the 19 Cityscapes classes)", K);
-    SLIDE_WINDOW_CHECKS("dclip_slide_eval_seg");
-    if (labels != nullptr) {
-        DCLIP_HOST_CHECK(lab_dt >= 0 && lab_dt <= 2,
-                         "dclip_slide_eval_seg: lab_dt=%d: labels int64 (0), int32 (1) or uint8 (2)", lab_dt);
-        DCLIP_HOST_CHECK(cm && loss_sum && count, "dclip_slide_eval_seg: cm, loss_sum and count required with labels");
+    WinTable wt;
+    WinShape shape;
+    if (int rc = check_windows("dclip_slide_eval_seg", low_dt, wins, nwin, B, h, w, wh, ww, H, W, wt, shape)) return rc;
+    if (int rc = check_seg_outputs("dclip_slide_eval_seg", labels, lab_dt, pred, cm, loss_sum, count)) return rc;
+    if (labels != nullptr)
         DCLIP_HOST_CHECK(ws != nullptr && ((uintptr_t)ws % 8) == 0,
                          "dclip_slide_eval_seg: ws=%p (dclip_slide_eval_ws_bytes(B, K, nwin) bytes, 8-byte aligned) "
                          "required", ws);
-    } else {
-        DCLIP_HOST_CHECK(!cm && !loss_sum && !count,
-                         "dclip_slide_eval_seg: cm, loss_sum and count must be null without labels");
-        DCLIP_HOST_CHECK(pred != nullptr, "dclip_slide_eval_seg: nothing to do (no labels, no pred)");
-    }
     hipStream_t st = (hipStream_t)stream;
-    if (low_dt == DCLIP_F32)
-        launch_seg<float>(wt, shape, B, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st);
-    else if (low_dt == DCLIP_BF16)
-        launch_seg<bf16>(wt, shape, B, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st);
-    else
-        launch_seg<f16>(wt, shape, B, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st);
+    EVAL_DISPATCH_LOW(low_dt, launch_seg<TL>(wt, shape, B, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }
@@ -457,22 +322,17 @@ extern "C" int dclip_slide_eval_depth(int low_dt, const dclip_window* wins, int 
                                       int ww, const float* target, const uint8_t* mask, int H, int W, float min_depth,
                                       float max_depth, int clamp_pred, float eps, float* up, double* sums, void* ws,
                                       void* stream) {
-    SLIDE_WINDOW_CHECKS("dclip_slide_eval_depth");
-    if (target != nullptr) {
-        DCLIP_HOST_CHECK(sums != nullptr, "dclip_slide_eval_depth: sums required with a target");
+    WinTable wt;
+    WinShape shape;
+    if (int rc = check_windows("dclip_slide_eval_depth", low_dt, wins, nwin, B, h, w, wh, ww, H, W, wt, shape)) return rc;
+    if (int rc = check_depth_outputs("dclip_slide_eval_depth", target, sums, up)) return rc;
+    if (target != nullptr)
         DCLIP_HOST_CHECK(ws != nullptr && ((uintptr_t)ws % 8) == 0,
                          "dclip_slide_eval_depth: ws=%p (dclip_slide_eval_ws_bytes(B, 1, nwin) bytes, 8-byte aligned) "
                          "required", ws);
-    } else {  // prediction only: mask, sums and ws are not touched
-        DCLIP_HOST_CHECK(up != nullptr, "dclip_slide_eval_depth: nothing to do (no target, no up)");
-    }
     hipStream_t st = (hipStream_t)stream;
-    if (low_dt == DCLIP_F32)
-        launch_depth<float>(wt, shape, B, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else if (low_dt == DCLIP_BF16)
-        launch_depth<bf16>(wt, shape, B, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else
-        launch_depth<f16>(wt, shape, B, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
+    EVAL_DISPATCH_LOW(low_dt, launch_depth<TL>(wt, shape, B, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums,
+                                               ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }

@@ -21,8 +21,9 @@
 // the per-workgroup records in the call's workspace and is written there by small launches of the
 // call itself, 128 entries of kernel arguments each (no hipMemcpy, no pinned memory: stream-ordered
 // and capturable).  The view table travels by value.  Whether a tile skips a window depends on the
-// tile alone: every thread reaches every barrier.  Records, f64 partials and the one-workgroup folds
-// are headeval's (eval_tile.h): no global atomics, the grid a function of the shapes alone, two runs
+// tile alone: every thread reaches every barrier.  The scoring epilogue (seg_score with one pixel a
+// thread, DepthSums), records, f64 partials and the one-workgroup folds are eval_tile.h's, as in
+// headeval.hip: no global atomics, the grid a function of the shapes alone, two runs
 // bitwise equal.  The depth kernel keeps headslide's thread-to-pixel map (8 x 128 tiles, 4 pixels a
 // thread), so one plain view at the image's size reproduces its f64 sums bit for bit.
 #include "eval_tile.h"
@@ -70,10 +71,7 @@ Tiling make_tiling(int B, int K, int px, SViewTable& vt, int H, int W) {
         t.lds = bytes > t.lds ? bytes : t.lds;
     }
     t.nrow = t.ncol = 0;  // per view, in the table
-    t.tiles_x = (W + t.tw - 1) / t.tw;
-    t.tiles_y = (H + TH - 1) / TH;
-    t.ntiles = B * t.tiles_y * t.tiles_x;  // < 2^31: B * H * W is
-    t.nwg = t.ntiles < NWG_MAX ? t.ntiles : NWG_MAX;
+    finish_tiling(t, B, H, W);
     return t;
 }
 
@@ -209,26 +207,22 @@ __global__ __launch_bounds__(256) void slide_tta_seg_kernel(SViewTable vt, const
     const int tid = threadIdx.x;
     const int tx = tid % TX, ty = tid / TX;
     const float inv_v = 1.f / (float)vt.n;
-    if constexpr (LAB) {
-        for (int e = tid; e < K * K + 1; e += blockDim.x) hist_s[e] = 0u;
-        __syncthreads();
-    }
+    if constexpr (LAB) hist_clear<K>(hist_s);
     double lsum = 0.0;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const int b = tile / (tl.tiles_x * tl.tiles_y);
-        const int y0 = ((tile / tl.tiles_x) % tl.tiles_y) * TH, x0 = (tile % tl.tiles_x) * tl.tw;
+        const auto [b, y0, x0] = tile_origin(tile, tl);
         const int y = y0 + ty, x = x0 + tx;
         const bool active = y < H && x < W;  // every thread stages every patch
-        float v[K];
+        float v[1][K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = 0.f;
+        for (int k = 0; k < K; ++k) v[0][k] = 0.f;
         for (int iv = 0; iv < vt.n; ++iv) {
             float u[1][K];
             view_values<TL, K, 1, false>(vt.v[iv], tab, low_s, b, y0, x0, tl.tw, H, W, y, x, active, u);
             if (!active) continue;
             if constexpr (!PROBS) {
 #pragma unroll
-                for (int k = 0; k < K; ++k) v[k] = add_rounded(v[k], u[0][k]);
+                for (int k = 0; k < K; ++k) v[0][k] = add_rounded(v[0][k], u[0][k]);
             } else {
                 float m = u[0][0];
 #pragma unroll
@@ -241,52 +235,20 @@ __global__ __launch_bounds__(256) void slide_tta_seg_kernel(SViewTable vt, const
                 }
                 const float inv = 1.f / s;
 #pragma unroll
-                for (int k = 0; k < K; ++k) v[k] += u[0][k] * inv;
+                for (int k = 0; k < K; ++k) v[0][k] += u[0][k] * inv;
             }
         }
         if (!active) continue;
         const int64_t pix = ((int64_t)b * H + y) * W + x;
 #pragma unroll
-        for (int k = 0; k < K; ++k) v[k] *= inv_v;
-        // argmax: the lowest class index among equal maxima (torch.argmax)
-        float m = v[0];
-        int a = 0;
-#pragma unroll
-        for (int k = 1; k < K; ++k)
-            if (v[k] > m) {
-                m = v[k];
-                a = k;
-            }
-        if constexpr (LAB) {
-            int t[4];
-            load_labels4(lab, lab_dt, pix, 1, false, t);
-            const int tp = t[0];
-            if (tp != ignore && tp >= 0 && tp < K) {
-                float vtgt = 0.f, s = 0.f;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    vtgt = k == tp ? v[k] : vtgt;
-                    if constexpr (!PROBS) s += __expf(v[k] - m);
-                }
-                if constexpr (PROBS) lsum += (double)(-__logf(vtgt));  // -log(mean prob[t])
-                else lsum += (double)(__logf(s) - (vtgt - m));         // -log softmax(mean)[t]
-                atomicAdd(&hist_s[tp * K + a], 1u);
-            }
-        }
-        if (pred != nullptr) pred[pix] = (uint8_t)a;
+        for (int k = 0; k < K; ++k) v[0][k] *= inv_v;
+        int t[4] = {-1, -1, -1, -1};
+        if constexpr (LAB) load_labels4(lab, lab_dt, pix, 1, false, t);
+        int am[1];
+        seg_score<K, 1, LAB, PROBS>(v, t, 1, ignore, hist_s, lsum, am);
+        if (pred != nullptr) pred[pix] = (uint8_t)am[0];
     }
-    if constexpr (LAB) {
-        char* rec = ws + (int64_t)blockIdx.x * record_bytes(K);
-        double a[1] = {lsum};
-        wg_partials<1>(a, red_s, (double*)rec);  // __syncthreads inside: every LDS add has landed after it
-        unsigned* hist = (unsigned*)(rec + NSUM * 8);
-        if (tid == 0) {
-            unsigned c = 0;
-            for (int e = 0; e < K * K; ++e) c += hist_s[e];
-            hist[K * K] = c;  // #valid
-        }
-        for (int e = tid; e < K * K; e += blockDim.x) hist[e] = hist_s[e];
-    }
+    if constexpr (LAB) seg_flush<K>(hist_s, lsum, red_s, ws);
 }
 
 // ----------------------------------------------------------------------------- depth
@@ -302,12 +264,9 @@ __global__ __launch_bounds__(256) void slide_tta_depth_kernel(SViewTable vt, con
     const int tid = threadIdx.x;
     const int tx = tid % TX, ty = tid / TX;
     const float inv_v = 1.f / (float)vt.n;
-    // sums[1..4], [9..11] in f64; the counts [0], [5..8] as integers (exact), widened at the end
-    double s_sq = 0.0, s_log = 0.0, s_abs = 0.0, s_sqrel = 0.0, s_msq = 0.0, s_d = 0.0, s_d2 = 0.0;
-    unsigned n_eval = 0, n_a1 = 0, n_a2 = 0, n_a3 = 0, n_mask = 0;
+    DepthSums acc;
     for (int tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
-        const int b = tile / (tl.tiles_x * tl.tiles_y);
-        const int y0 = ((tile / tl.tiles_x) % tl.tiles_y) * TH, x0 = (tile % tl.tiles_x) * tl.tw;
+        const auto [b, y0, x0] = tile_origin(tile, tl);
         const int y = y0 + ty, x = x0 + 4 * tx;
         const bool active = y < H && x < W;
         float u[4] = {0.f, 0.f, 0.f, 0.f};
@@ -323,67 +282,10 @@ __global__ __launch_bounds__(256) void slide_tta_depth_kernel(SViewTable vt, con
         const int64_t pix = ((int64_t)b * H + y) * W + x;
 #pragma unroll
         for (int p = 0; p < 4; ++p) u[p] *= inv_v;
-        if (up != nullptr) {
-            if (vec) {
-                *(float4*)(up + pix) = make_float4(u[0], u[1], u[2], u[3]);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    if (p < n) up[pix + p] = u[p];
-            }
-        }
-        if constexpr (TGT) {
-            float tg[4] = {0.f, 0.f, 0.f, 0.f};
-            bool tm[4];
-            if (vec) {
-                const float4 a = *(const float4*)(gt + pix);
-                tg[0] = a.x; tg[1] = a.y; tg[2] = a.z; tg[3] = a.w;
-                const uint32_t mk = mask ? *(const uint32_t*)(mask + pix) : 0x01010101u;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) tm[p] = ((mk >> (8 * p)) & 0xffu) != 0;
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    tm[p] = false;
-                    if (p < n) {
-                        tg[p] = gt[pix + p];
-                        tm[p] = mask == nullptr || mask[pix + p] != 0;
-                    }
-                }
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                if (!tm[p]) continue;
-                const float gtv = tg[p];
-                // the trainer's masked RMSE (unclamped) and the SILog pass-0 sums, d as dclip_upsample_silog
-                ++n_mask;
-                const float dm = gtv - u[p];
-                s_msq += (double)(dm * dm);
-                const float d = logf(fmaxf(u[p], eps)) - logf(fmaxf(gtv, eps));
-                s_d += (double)d;
-                s_d2 += (double)d * (double)d;
-                // compute_depth_errors: mask && min <= gt <= max, optionally clamped prediction
-                if (!(gtv >= dmin && gtv <= dmax)) continue;
-                const float pr = clamp_pred ? fminf(fmaxf(u[p], dmin), dmax) : u[p];
-                ++n_eval;
-                const float thr = fmaxf(gtv / pr, pr / gtv);
-                n_a1 += thr < 1.25f ? 1u : 0u;
-                n_a2 += thr < 1.5625f ? 1u : 0u;
-                n_a3 += thr < 1.953125f ? 1u : 0u;
-                const float df = gtv - pr;
-                const float dl = logf(gtv) - logf(pr);
-                s_sq += (double)(df * df);
-                s_log += (double)(dl * dl);
-                s_abs += (double)(fabsf(df) / gtv);
-                s_sqrel += (double)(df * df / gtv);
-            }
-        }
+        store_up4(up, pix, n, vec != 0, u);
+        if constexpr (TGT) acc.score4(u, gt, mask, pix, n, vec != 0, dmin, dmax, clamp_pred, eps);
     }
-    if constexpr (TGT) {
-        double a[NSUM] = {(double)n_eval, s_sq,          s_log,          s_abs, s_sqrel, (double)n_a1,
-                          (double)n_a2,   (double)n_a3, (double)n_mask, s_msq, s_d,     s_d2};
-        wg_partials<NSUM>(a, red_s, (double*)(ws + (int64_t)blockIdx.x * record_bytes(1)));
-    }
+    if constexpr (TGT) acc.flush(red_s, ws);
 }
 
 // the window table behind the K-class records of `ws`
@@ -417,8 +319,7 @@ template <typename TL>
 void launch_depth(const SViewTable& vt, const Tiling& tl, const dclip_window* tab, int H, int W, const float* gt,
                   const uint8_t* mask, float dmin, float dmax, int clamp_pred, float eps, float* up, double* sums,
                   void* ws, hipStream_t st) {
-    const int vec = W % 4 == 0 && (gt == nullptr || (uintptr_t)gt % 16 == 0) &&
-                    (mask == nullptr || (uintptr_t)mask % 4 == 0) && (up == nullptr || (uintptr_t)up % 16 == 0);
+    const int vec = depth_aligned(gt, mask, up, W);
     if (gt != nullptr) {
         slide_tta_depth_kernel<TL, true><<<tl.nwg, 256, tl.lds, st>>>(vt, tab, H, W, tl, gt, mask, dmin, dmax,
                                                                       clamp_pred, eps, vec, up, (char*)ws);
@@ -504,26 +405,12 @@ extern "C" int dclip_slide_tta_eval_seg(int low_dt, const dclip_slide_view* view
     if (int rc = check_tables("dclip_slide_tta_eval_seg", low_dt, views, nviews, wins, nwin_total, B, K, 1, H, W, ws, vt,
                               tl))
         return rc;
-    if (labels != nullptr) {
-        DCLIP_HOST_CHECK(lab_dt >= 0 && lab_dt <= 2,
-                         "dclip_slide_tta_eval_seg: lab_dt=%d: labels int64 (0), int32 (1) or uint8 (2)", lab_dt);
-        DCLIP_HOST_CHECK(cm && loss_sum && count,
-                         "dclip_slide_tta_eval_seg: cm, loss_sum and count required with labels");
-    } else {
-        DCLIP_HOST_CHECK(!cm && !loss_sum && !count,
-                         "dclip_slide_tta_eval_seg: cm, loss_sum and count must be null without labels");
-        DCLIP_HOST_CHECK(pred != nullptr, "dclip_slide_tta_eval_seg: nothing to do (no labels, no pred)");
-    }
+    if (int rc = check_seg_outputs("dclip_slide_tta_eval_seg", labels, lab_dt, pred, cm, loss_sum, count)) return rc;
     hipStream_t st = (hipStream_t)stream;
     dclip_window* tab = table_of(ws, K);
     write_table(wins, nwin_total, tab, st);
-#define SLIDE_TTA_SEG(TL)                                                                                          \
-    (average ? launch_seg<TL, true>(vt, tl, tab, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st) \
-             : launch_seg<TL, false>(vt, tl, tab, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st))
-    if (low_dt == DCLIP_F32) SLIDE_TTA_SEG(float);
-    else if (low_dt == DCLIP_BF16) SLIDE_TTA_SEG(bf16);
-    else SLIDE_TTA_SEG(f16);
-#undef SLIDE_TTA_SEG
+    EVAL_DISPATCH_LOW(low_dt, (average ? launch_seg<TL, true> : launch_seg<TL, false>)(
+                                  vt, tl, tab, H, W, labels, lab_dt, ignore_index, pred, cm, loss_sum, count, ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }
@@ -537,20 +424,12 @@ extern "C" int dclip_slide_tta_eval_depth(int low_dt, const dclip_slide_view* vi
     if (int rc = check_tables("dclip_slide_tta_eval_depth", low_dt, views, nviews, wins, nwin_total, B, 1, 4, H, W, ws,
                               vt, tl))
         return rc;
-    if (target != nullptr) {
-        DCLIP_HOST_CHECK(sums != nullptr, "dclip_slide_tta_eval_depth: sums required with a target");
-    } else {  // prediction only: mask and sums are not touched
-        DCLIP_HOST_CHECK(up != nullptr, "dclip_slide_tta_eval_depth: nothing to do (no target, no up)");
-    }
+    if (int rc = check_depth_outputs("dclip_slide_tta_eval_depth", target, sums, up)) return rc;
     hipStream_t st = (hipStream_t)stream;
     dclip_window* tab = table_of(ws, 1);
     write_table(wins, nwin_total, tab, st);
-    if (low_dt == DCLIP_F32)
-        launch_depth<float>(vt, tl, tab, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else if (low_dt == DCLIP_BF16)
-        launch_depth<bf16>(vt, tl, tab, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
-    else
-        launch_depth<f16>(vt, tl, tab, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up, sums, ws, st);
+    EVAL_DISPATCH_LOW(low_dt, launch_depth<TL>(vt, tl, tab, H, W, target, mask, min_depth, max_depth, clamp_pred, eps, up,
+                                               sums, ws, st));
     DCLIP_LAUNCH_CHECK();
     return 0;
 }

@@ -902,6 +902,48 @@ Tensor eval_ws(const Tensor& low, int64_t K) {
                      like(low, at::kByte));
 }
 
+// The *_seg_update ops: checks `labels`, `cm` and `ce_sums` against the low-res logits `l0`, takes
+// (H, W) from the labels, allocates the class map (when want_pred) and the call's #valid, runs
+// launch(H, W, pred, count) (the op's workspace and C entry point) and adds the count beside the CE sum.
+template <typename Launch>
+c10::optional<Tensor> seg_update_with(const char* op, const Tensor& l0, const Tensor& labels, Tensor& cm,
+                                      Tensor& ce_sums, bool want_pred, Launch launch) {
+    check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
+    TORCH_CHECK(l0.dim() == 4 && labels.dim() == 3 && labels.size(0) == l0.size(0), op, ": shapes");
+    const int64_t K = l0.size(1);
+    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, op, ": cm must be int64 (K, K)");
+    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2, op, ": ce_sums must be float64[2]");
+    c10::DeviceGuard g(l0.device());
+    const int64_t H = labels.size(1), W = labels.size(2);
+    Tensor pred = want_pred ? at::empty({l0.size(0), H, W}, like(l0, at::kByte)) : Tensor();
+    Tensor cnt = at::zeros({1}, like(l0, at::kLong));
+    launch((int)H, (int)W, ptr<uint8_t>(pred), (unsigned long long*)cnt.data_ptr());
+    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
+    if (!want_pred) return c10::nullopt;
+    return pred;
+}
+
+// The *_depth_update ops: checks `target`, `mask` and `sums` against the low-res prediction `p0`, takes
+// (H, W) from the target, allocates the resized map (when want_up) and runs launch(H, W, up).
+template <typename Launch>
+c10::optional<Tensor> depth_update_with(const char* op, const Tensor& p0, const Tensor& target,
+                                        const c10::optional<Tensor>& mask, Tensor& sums, bool want_up,
+                                        Launch launch) {
+    check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
+    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == p0.size(0), op,
+                ": target (B, H, W) fp32");
+    const bool has_mask = mask.has_value() && mask->defined();
+    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()), op,
+                ": mask (B, H, W) uint8");
+    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12, op, ": sums must be float64[12]");
+    c10::DeviceGuard g(p0.device());
+    const int64_t H = target.size(1), W = target.size(2);
+    Tensor up = want_up ? at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat)) : Tensor();
+    launch((int)H, (int)W, ptr<float>(up));
+    if (!want_up) return c10::nullopt;
+    return up;
+}
+
 // argmax class map u8 (B, H, W) of the resized logits
 Tensor upsample_argmax(const Tensor& logits, int64_t H, int64_t W) {
     check_gpu(logits, "logits");
@@ -919,49 +961,32 @@ Tensor upsample_argmax(const Tensor& logits, int64_t H, int64_t W) {
 // the class map when want_pred
 c10::optional<Tensor> seg_update(const Tensor& logits, const Tensor& labels, int64_t ignore_index, Tensor& cm,
                                  Tensor& ce_sums, bool want_pred) {
-    check_gpu(logits, "logits"); check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
-    TORCH_CHECK(logits.dim() == 4 && labels.dim() == 3 && labels.size(0) == logits.size(0), "seg_update: shapes");
-    const int64_t K = logits.size(1);
-    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, "seg_update: cm must be int64 (K, K)");
-    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2, "seg_update: ce_sums must be float64[2]");
-    c10::DeviceGuard g(logits.device());
-    const int64_t H = labels.size(1), W = labels.size(2);
-    Tensor pred = want_pred ? at::empty({logits.size(0), H, W}, like(logits, at::kByte)) : Tensor();
-    Tensor cnt = at::zeros({1}, like(logits, at::kLong));
-    Tensor ws = eval_ws(logits, K);
-    DCLIP_CALL(dclip_upsample_eval_seg(dt_code(logits.scalar_type()), logits.data_ptr(), (int)logits.size(0), (int)K,
-                                       (int)logits.size(2), (int)logits.size(3), labels.data_ptr(),
-                                       lab_code(labels.scalar_type()), (int)H, (int)W, (int)ignore_index,
-                                       ptr<uint8_t>(pred), ptr<int64_t>(cm), ptr<double>(ce_sums),
-                                       (unsigned long long*)cnt.data_ptr(), ws.data_ptr(), stream_of(logits)));
-    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
-    if (!want_pred) return c10::nullopt;
-    return pred;
+    check_gpu(logits, "logits");
+    return seg_update_with("seg_update", logits, labels, cm, ce_sums, want_pred,
+                           [&](int H, int W, uint8_t* pred, unsigned long long* cnt) {
+        Tensor ws = eval_ws(logits, logits.size(1));
+        DCLIP_CALL(dclip_upsample_eval_seg(dt_code(logits.scalar_type()), logits.data_ptr(), (int)logits.size(0),
+                                           (int)logits.size(1), (int)logits.size(2), (int)logits.size(3),
+                                           labels.data_ptr(), lab_code(labels.scalar_type()), H, W, (int)ignore_index,
+                                           pred, ptr<int64_t>(cm), ptr<double>(ce_sums), cnt, ws.data_ptr(),
+                                           stream_of(logits)));
+    });
 }
 
 // sums (f64[12], dclip.h) += the depth sums of the resized prediction; the resized map (B, 1, H, W) when want_up
 c10::optional<Tensor> depth_update(const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& mask,
                                    double min_depth, double max_depth, bool clamp_pred, double eps, Tensor& sums,
                                    bool want_up) {
-    check_gpu(pred, "pred"); check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
+    check_gpu(pred, "pred");
     TORCH_CHECK(pred.dim() == 4 && pred.size(1) == 1, "depth_update: pred (B, 1, h, w)");
-    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == pred.size(0),
-                "depth_update: target (B, H, W) fp32");
-    const bool has_mask = mask.has_value() && mask->defined();
-    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()),
-                "depth_update: mask (B, H, W) uint8");
-    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12, "depth_update: sums must be float64[12]");
-    c10::DeviceGuard g(pred.device());
-    const int64_t H = target.size(1), W = target.size(2);
-    Tensor up = want_up ? at::empty({pred.size(0), 1, H, W}, like(pred, at::kFloat)) : Tensor();
-    Tensor ws = eval_ws(pred, 1);
-    DCLIP_CALL(dclip_upsample_eval_depth(dt_code(pred.scalar_type()), pred.data_ptr(), (int)pred.size(0),
-                                         (int)pred.size(2), (int)pred.size(3), ptr<float>(target), optr<uint8_t>(mask),
-                                         (int)H, (int)W, (float)min_depth, (float)max_depth, clamp_pred ? 1 : 0,
-                                         (float)eps, ptr<float>(up), ptr<double>(sums), ws.data_ptr(),
-                                         stream_of(pred)));
-    if (!want_up) return c10::nullopt;
-    return up;
+    return depth_update_with("depth_update", pred, target, mask, sums, want_up, [&](int H, int W, float* up) {
+        Tensor ws = eval_ws(pred, 1);
+        DCLIP_CALL(dclip_upsample_eval_depth(dt_code(pred.scalar_type()), pred.data_ptr(), (int)pred.size(0),
+                                             (int)pred.size(2), (int)pred.size(3), ptr<float>(target),
+                                             optr<uint8_t>(mask), H, W, (float)min_depth, (float)max_depth,
+                                             clamp_pred ? 1 : 0, (float)eps, up, ptr<double>(sums), ws.data_ptr(),
+                                             stream_of(pred)));
+    });
 }
 
 // ----------------------------------------------------------------------------- fused test-time ensembling
@@ -1008,25 +1033,14 @@ c10::optional<Tensor> ensemble_seg_update(at::TensorList logits, at::IntArrayRef
                                           bool want_pred) {
     const std::vector<dclip_view> views = ensemble_views(logits, flips, false, "ensemble_seg_update");
     const Tensor& l0 = logits[0];
-    check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
-    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == l0.size(0), "ensemble_seg_update: shapes");
-    const int64_t K = l0.size(1);
-    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, "ensemble_seg_update: cm must be int64 (K, K)");
-    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2,
-                "ensemble_seg_update: ce_sums must be float64[2]");
-    c10::DeviceGuard g(l0.device());
-    const int64_t H = labels.size(1), W = labels.size(2);
-    Tensor pred = want_pred ? at::empty({l0.size(0), H, W}, like(l0, at::kByte)) : Tensor();
-    Tensor cnt = at::zeros({1}, like(l0, at::kLong));
-    Tensor ws = ensemble_ws(l0, K, views.size());
-    DCLIP_CALL(dclip_ensemble_eval_seg(dt_code(l0.scalar_type()), views.data(), (int)views.size(), (int)l0.size(0),
-                                       (int)K, probs ? 1 : 0, labels.data_ptr(), lab_code(labels.scalar_type()),
-                                       (int)H, (int)W, (int)ignore_index, ptr<uint8_t>(pred), ptr<int64_t>(cm),
-                                       ptr<double>(ce_sums), (unsigned long long*)cnt.data_ptr(), ws.data_ptr(),
-                                       stream_of(l0)));
-    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
-    if (!want_pred) return c10::nullopt;
-    return pred;
+    return seg_update_with("ensemble_seg_update", l0, labels, cm, ce_sums, want_pred,
+                           [&](int H, int W, uint8_t* pred, unsigned long long* cnt) {
+        Tensor ws = ensemble_ws(l0, l0.size(1), views.size());
+        DCLIP_CALL(dclip_ensemble_eval_seg(dt_code(l0.scalar_type()), views.data(), (int)views.size(), (int)l0.size(0),
+                                           (int)l0.size(1), probs ? 1 : 0, labels.data_ptr(),
+                                           lab_code(labels.scalar_type()), H, W, (int)ignore_index, pred,
+                                           ptr<int64_t>(cm), ptr<double>(ce_sums), cnt, ws.data_ptr(), stream_of(l0)));
+    });
 }
 
 // f32 (B, 1, H, W): the mean of the views' resized, mirrored-back depth predictions
@@ -1047,24 +1061,13 @@ c10::optional<Tensor> ensemble_depth_update(at::TensorList preds, at::IntArrayRe
                                             bool clamp_pred, double eps, Tensor& sums, bool want_up) {
     const std::vector<dclip_view> views = ensemble_views(preds, flips, true, "ensemble_depth_update");
     const Tensor& p0 = preds[0];
-    check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
-    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == p0.size(0),
-                "ensemble_depth_update: target (B, H, W) fp32");
-    const bool has_mask = mask.has_value() && mask->defined();
-    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()),
-                "ensemble_depth_update: mask (B, H, W) uint8");
-    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12,
-                "ensemble_depth_update: sums must be float64[12]");
-    c10::DeviceGuard g(p0.device());
-    const int64_t H = target.size(1), W = target.size(2);
-    Tensor up = want_up ? at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat)) : Tensor();
-    Tensor ws = ensemble_ws(p0, 1, views.size());
-    DCLIP_CALL(dclip_ensemble_eval_depth(dt_code(p0.scalar_type()), views.data(), (int)views.size(), (int)p0.size(0),
-                                         ptr<float>(target), optr<uint8_t>(mask), (int)H, (int)W, (float)min_depth,
-                                         (float)max_depth, clamp_pred ? 1 : 0, (float)eps, ptr<float>(up),
-                                         ptr<double>(sums), ws.data_ptr(), stream_of(p0)));
-    if (!want_up) return c10::nullopt;
-    return up;
+    return depth_update_with("ensemble_depth_update", p0, target, mask, sums, want_up, [&](int H, int W, float* up) {
+        Tensor ws = ensemble_ws(p0, 1, views.size());
+        DCLIP_CALL(dclip_ensemble_eval_depth(dt_code(p0.scalar_type()), views.data(), (int)views.size(),
+                                             (int)p0.size(0), ptr<float>(target), optr<uint8_t>(mask), H, W,
+                                             (float)min_depth, (float)max_depth, clamp_pred ? 1 : 0, (float)eps, up,
+                                             ptr<double>(sums), ws.data_ptr(), stream_of(p0)));
+    });
 }
 
 // ----------------------------------------------------------------------------- fused sliding-window inference
@@ -1113,25 +1116,15 @@ c10::optional<Tensor> slide_seg_update(at::TensorList logits, at::IntArrayRef or
                                        bool want_pred) {
     const std::vector<dclip_window> wins = slide_windows(logits, origins, false, "slide_seg_update");
     const Tensor& l0 = logits[0];
-    check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
-    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == l0.size(0), "slide_seg_update: shapes");
-    const int64_t K = l0.size(1);
-    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, "slide_seg_update: cm must be int64 (K, K)");
-    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2,
-                "slide_seg_update: ce_sums must be float64[2]");
-    c10::DeviceGuard g(l0.device());
-    const int64_t H = labels.size(1), W = labels.size(2);
-    Tensor pred = want_pred ? at::empty({l0.size(0), H, W}, like(l0, at::kByte)) : Tensor();
-    Tensor cnt = at::zeros({1}, like(l0, at::kLong));
-    Tensor ws = slide_ws(l0, K, wins.size());
-    DCLIP_CALL(dclip_slide_eval_seg(dt_code(l0.scalar_type()), wins.data(), (int)wins.size(), (int)l0.size(0), (int)K,
-                                    (int)l0.size(2), (int)l0.size(3), (int)wh, (int)ww, labels.data_ptr(),
-                                    lab_code(labels.scalar_type()), (int)H, (int)W, (int)ignore_index,
-                                    ptr<uint8_t>(pred), ptr<int64_t>(cm), ptr<double>(ce_sums),
-                                    (unsigned long long*)cnt.data_ptr(), ws.data_ptr(), stream_of(l0)));
-    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
-    if (!want_pred) return c10::nullopt;
-    return pred;
+    return seg_update_with("slide_seg_update", l0, labels, cm, ce_sums, want_pred,
+                           [&](int H, int W, uint8_t* pred, unsigned long long* cnt) {
+        Tensor ws = slide_ws(l0, l0.size(1), wins.size());
+        DCLIP_CALL(dclip_slide_eval_seg(dt_code(l0.scalar_type()), wins.data(), (int)wins.size(), (int)l0.size(0),
+                                        (int)l0.size(1), (int)l0.size(2), (int)l0.size(3), (int)wh, (int)ww,
+                                        labels.data_ptr(), lab_code(labels.scalar_type()), H, W, (int)ignore_index,
+                                        pred, ptr<int64_t>(cm), ptr<double>(ce_sums), cnt, ws.data_ptr(),
+                                        stream_of(l0)));
+    });
 }
 
 // f32 (B, 1, H, W): the mean of the covering windows' depth predictions resized to wh x ww
@@ -1152,24 +1145,14 @@ c10::optional<Tensor> slide_depth_update(at::TensorList preds, at::IntArrayRef o
                                          double max_depth, bool clamp_pred, double eps, Tensor& sums, bool want_up) {
     const std::vector<dclip_window> wins = slide_windows(preds, origins, true, "slide_depth_update");
     const Tensor& p0 = preds[0];
-    check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
-    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == p0.size(0),
-                "slide_depth_update: target (B, H, W) fp32");
-    const bool has_mask = mask.has_value() && mask->defined();
-    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()),
-                "slide_depth_update: mask (B, H, W) uint8");
-    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12, "slide_depth_update: sums must be float64[12]");
-    c10::DeviceGuard g(p0.device());
-    const int64_t H = target.size(1), W = target.size(2);
-    Tensor up = want_up ? at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat)) : Tensor();
-    Tensor ws = slide_ws(p0, 1, wins.size());
-    DCLIP_CALL(dclip_slide_eval_depth(dt_code(p0.scalar_type()), wins.data(), (int)wins.size(), (int)p0.size(0),
-                                      (int)p0.size(2), (int)p0.size(3), (int)wh, (int)ww, ptr<float>(target),
-                                      optr<uint8_t>(mask), (int)H, (int)W, (float)min_depth, (float)max_depth,
-                                      clamp_pred ? 1 : 0, (float)eps, ptr<float>(up), ptr<double>(sums), ws.data_ptr(),
-                                      stream_of(p0)));
-    if (!want_up) return c10::nullopt;
-    return up;
+    return depth_update_with("slide_depth_update", p0, target, mask, sums, want_up, [&](int H, int W, float* up) {
+        Tensor ws = slide_ws(p0, 1, wins.size());
+        DCLIP_CALL(dclip_slide_eval_depth(dt_code(p0.scalar_type()), wins.data(), (int)wins.size(), (int)p0.size(0),
+                                          (int)p0.size(2), (int)p0.size(3), (int)wh, (int)ww, ptr<float>(target),
+                                          optr<uint8_t>(mask), H, W, (float)min_depth, (float)max_depth,
+                                          clamp_pred ? 1 : 0, (float)eps, up, ptr<double>(sums), ws.data_ptr(),
+                                          stream_of(p0)));
+    });
 }
 
 // ----------------------------------------------------------------------------- fused sliding windows under TTA
@@ -1242,25 +1225,15 @@ c10::optional<Tensor> slide_tta_seg_update(at::TensorList logits, at::IntArrayRe
                                            Tensor& ce_sums, bool want_pred) {
     const SlideTtaTables t = slide_tta_tables(logits, views, origins, false, "slide_tta_seg_update");
     const Tensor& l0 = logits[0];
-    check_gpu(labels, "labels"); check_gpu(cm, "cm"); check_gpu(ce_sums, "ce_sums");
-    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == l0.size(0), "slide_tta_seg_update: shapes");
-    const int64_t K = l0.size(1);
-    TORCH_CHECK(cm.scalar_type() == at::kLong && cm.numel() == K * K, "slide_tta_seg_update: cm must be int64 (K, K)");
-    TORCH_CHECK(ce_sums.scalar_type() == at::kDouble && ce_sums.numel() == 2,
-                "slide_tta_seg_update: ce_sums must be float64[2]");
-    c10::DeviceGuard g(l0.device());
-    const int64_t H = labels.size(1), W = labels.size(2);
-    Tensor pred = want_pred ? at::empty({l0.size(0), H, W}, like(l0, at::kByte)) : Tensor();
-    Tensor cnt = at::zeros({1}, like(l0, at::kLong));
-    Tensor ws = slide_tta_ws(l0, K, t);
-    DCLIP_CALL(dclip_slide_tta_eval_seg(dt_code(l0.scalar_type()), t.views.data(), (int)t.views.size(), t.wins.data(),
-                                        (int)t.wins.size(), (int)l0.size(0), (int)K, probs ? 1 : 0, labels.data_ptr(),
-                                        lab_code(labels.scalar_type()), (int)H, (int)W, (int)ignore_index,
-                                        ptr<uint8_t>(pred), ptr<int64_t>(cm), ptr<double>(ce_sums),
-                                        (unsigned long long*)cnt.data_ptr(), ws.data_ptr(), stream_of(l0)));
-    ce_sums.view({2}).select(0, 1).add_(cnt.select(0, 0));  // the count beside the sum, as f64 (exact below 2^53)
-    if (!want_pred) return c10::nullopt;
-    return pred;
+    return seg_update_with("slide_tta_seg_update", l0, labels, cm, ce_sums, want_pred,
+                           [&](int H, int W, uint8_t* pred, unsigned long long* cnt) {
+        Tensor ws = slide_tta_ws(l0, l0.size(1), t);
+        DCLIP_CALL(dclip_slide_tta_eval_seg(dt_code(l0.scalar_type()), t.views.data(), (int)t.views.size(),
+                                            t.wins.data(), (int)t.wins.size(), (int)l0.size(0), (int)l0.size(1),
+                                            probs ? 1 : 0, labels.data_ptr(), lab_code(labels.scalar_type()), H, W,
+                                            (int)ignore_index, pred, ptr<int64_t>(cm), ptr<double>(ce_sums), cnt,
+                                            ws.data_ptr(), stream_of(l0)));
+    });
 }
 
 // f32 (B, 1, H, W): the mean over the views of their depth slide results resized to H x W
@@ -1283,25 +1256,14 @@ c10::optional<Tensor> slide_tta_depth_update(at::TensorList preds, at::IntArrayR
                                              bool want_up) {
     const SlideTtaTables t = slide_tta_tables(preds, views, origins, true, "slide_tta_depth_update");
     const Tensor& p0 = preds[0];
-    check_gpu(target, "target"); check_opt(mask, "mask"); check_gpu(sums, "sums");
-    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == p0.size(0),
-                "slide_tta_depth_update: target (B, H, W) fp32");
-    const bool has_mask = mask.has_value() && mask->defined();
-    TORCH_CHECK(!has_mask || (mask->scalar_type() == at::kByte && mask->sizes() == target.sizes()),
-                "slide_tta_depth_update: mask (B, H, W) uint8");
-    TORCH_CHECK(sums.scalar_type() == at::kDouble && sums.numel() == 12,
-                "slide_tta_depth_update: sums must be float64[12]");
-    c10::DeviceGuard g(p0.device());
-    const int64_t H = target.size(1), W = target.size(2);
-    Tensor up = want_up ? at::empty({p0.size(0), 1, H, W}, like(p0, at::kFloat)) : Tensor();
-    Tensor ws = slide_tta_ws(p0, 1, t);
-    DCLIP_CALL(dclip_slide_tta_eval_depth(dt_code(p0.scalar_type()), t.views.data(), (int)t.views.size(), t.wins.data(),
-                                          (int)t.wins.size(), (int)p0.size(0), ptr<float>(target), optr<uint8_t>(mask),
-                                          (int)H, (int)W, (float)min_depth, (float)max_depth, clamp_pred ? 1 : 0,
-                                          (float)eps, ptr<float>(up), ptr<double>(sums), ws.data_ptr(),
-                                          stream_of(p0)));
-    if (!want_up) return c10::nullopt;
-    return up;
+    return depth_update_with("slide_tta_depth_update", p0, target, mask, sums, want_up, [&](int H, int W, float* up) {
+        Tensor ws = slide_tta_ws(p0, 1, t);
+        DCLIP_CALL(dclip_slide_tta_eval_depth(dt_code(p0.scalar_type()), t.views.data(), (int)t.views.size(),
+                                              t.wins.data(), (int)t.wins.size(), (int)p0.size(0), ptr<float>(target),
+                                              optr<uint8_t>(mask), H, W, (float)min_depth, (float)max_depth,
+                                              clamp_pred ? 1 : 0, (float)eps, up, ptr<double>(sums), ws.data_ptr(),
+                                              stream_of(p0)));
+    });
 }
 
 // ----------------------------------------------------------------------------- optimizer

@@ -345,6 +345,42 @@ class Evaluator:
         for t in (self.cm, self.ce_sums, self.depth_sums):
             t.zero_()
 
+    def _own(self, per_call):
+        """the call's own zeroed sums (per_call=True), or None: the fused ops add to the running state"""
+        if not per_call:
+            return None
+        return {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
+                "depth_sums": torch.zeros_like(self.depth_sums)}
+
+    def _add_back(self, own, *keys):
+        """the call's own sums into the running state"""
+        if own is not None:
+            for k in keys:
+                getattr(self, k).add_(own[k])
+
+    def _seg_args(self, maps, what, seg_target, own):
+        """(contiguous low-res maps, labels (B, H, W) in a dtype the kernels read, cm, ce_sums)"""
+        for v in maps:
+            _need_gpu(v, what)
+            if v.shape[1] != self.num_classes:
+                raise ValueError(f"Evaluator: {v.shape[1]} classes, built for {self.num_classes}")
+        lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
+        if lab.dtype not in _LAB_DTYPES:
+            lab = lab.long()
+        cm, ce = (self.cm, self.ce_sums) if own is None else (own["cm"], own["ce_sums"])
+        return [v.detach().contiguous() for v in maps], lab.contiguous(), cm, ce
+
+    def _depth_args(self, maps, what, depth_target, depth_mask, own):
+        """(contiguous low-res maps, target (B, H, W) fp32, mask (B, H, W) uint8 or None, sums)"""
+        for v in maps:
+            _need_gpu(v, what)
+        B = depth_target.shape[0]
+        tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
+        mk = None
+        if depth_mask is not None:
+            mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
+        return [v.detach().contiguous() for v in maps], tg, mk, self.depth_sums if own is None else own["depth_sums"]
+
     def update(self, seg_lowres=None, depth_lowres=None, seg_target=None, depth_target=None, depth_mask=None,
                per_call=False):
         """Add one batch: `seg_lowres` (B, K, h, w) with `seg_target` (B, H, W) int64 / int32 / uint8,
@@ -352,34 +388,15 @@ class Evaluator:
         bool / uint8, None = all valid).  Returns None, or with per_call=True the call's own
         {'cm', 'ce_sums', 'depth_sums'} (device tensors, also added to the running state)."""
         E = _E()
-        own = None
-        if per_call:
-            own = {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
-                   "depth_sums": torch.zeros_like(self.depth_sums)}
+        own = self._own(per_call)
         if seg_lowres is not None and seg_target is not None:
-            _need_gpu(seg_lowres, "seg_lowres")
-            if seg_lowres.shape[1] != self.num_classes:
-                raise ValueError(f"Evaluator: {seg_lowres.shape[1]} classes, built for {self.num_classes}")
-            lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
-            if lab.dtype not in _LAB_DTYPES:
-                lab = lab.long()
-            cm, ce = (own["cm"], own["ce_sums"]) if per_call else (self.cm, self.ce_sums)
-            E.seg_update(seg_lowres.detach().contiguous(), lab.contiguous(), self.ignore_index, cm, ce, False)
-            if per_call:
-                self.cm += cm
-                self.ce_sums += ce
+            (low,), lab, cm, ce = self._seg_args([seg_lowres], "seg_lowres", seg_target, own)
+            E.seg_update(low, lab, self.ignore_index, cm, ce, False)
+            self._add_back(own, "cm", "ce_sums")
         if depth_lowres is not None and depth_target is not None:
-            _need_gpu(depth_lowres, "depth_lowres")
-            B = depth_target.shape[0]
-            tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
-            mk = None
-            if depth_mask is not None:
-                mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
-            sums = own["depth_sums"] if per_call else self.depth_sums
-            E.depth_update(depth_lowres.detach().contiguous(), tg, mk, self.min_depth, self.max_depth,
-                           self.clamp_pred, self.eps, sums, False)
-            if per_call:
-                self.depth_sums += sums
+            (low,), tg, mk, sums = self._depth_args([depth_lowres], "depth_lowres", depth_target, depth_mask, own)
+            E.depth_update(low, tg, mk, self.min_depth, self.max_depth, self.clamp_pred, self.eps, sums, False)
+            self._add_back(own, "depth_sums")
         return own
 
     def update_views(self, seg_views=None, depth_views=None, flips=(), seg_target=None, depth_target=None,
@@ -393,37 +410,16 @@ class Evaluator:
         probs = _probs(average)
         E = _E()
         flips = [int(f) for f in flips]
-        own = None
-        if per_call:
-            own = {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
-                   "depth_sums": torch.zeros_like(self.depth_sums)}
+        own = self._own(per_call)
         if seg_views and seg_target is not None:
-            for v in seg_views:
-                _need_gpu(v, "seg_views")
-                if v.shape[1] != self.num_classes:
-                    raise ValueError(f"Evaluator: {v.shape[1]} classes, built for {self.num_classes}")
-            lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
-            if lab.dtype not in _LAB_DTYPES:
-                lab = lab.long()
-            cm, ce = (own["cm"], own["ce_sums"]) if per_call else (self.cm, self.ce_sums)
-            E.ensemble_seg_update([v.detach().contiguous() for v in seg_views], flips, lab.contiguous(),
-                                  self.ignore_index, probs, cm, ce, False)
-            if per_call:
-                self.cm += cm
-                self.ce_sums += ce
+            lows, lab, cm, ce = self._seg_args(seg_views, "seg_views", seg_target, own)
+            E.ensemble_seg_update(lows, flips, lab, self.ignore_index, probs, cm, ce, False)
+            self._add_back(own, "cm", "ce_sums")
         if depth_views and depth_target is not None:
-            for v in depth_views:
-                _need_gpu(v, "depth_views")
-            B = depth_target.shape[0]
-            tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
-            mk = None
-            if depth_mask is not None:
-                mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
-            sums = own["depth_sums"] if per_call else self.depth_sums
-            E.ensemble_depth_update([v.detach().contiguous() for v in depth_views], flips, tg, mk, self.min_depth,
-                                    self.max_depth, self.clamp_pred, self.eps, sums, False)
-            if per_call:
-                self.depth_sums += sums
+            lows, tg, mk, sums = self._depth_args(depth_views, "depth_views", depth_target, depth_mask, own)
+            E.ensemble_depth_update(lows, flips, tg, mk, self.min_depth, self.max_depth, self.clamp_pred, self.eps,
+                                    sums, False)
+            self._add_back(own, "depth_sums")
         return own
 
     def update_windows(self, seg_lows=None, depth_lows=None, window_size=None, origins=(), seg_target=None,
@@ -437,37 +433,16 @@ class Evaluator:
         E = _E()
         wh, ww = int(window_size[0]), int(window_size[1])
         flat = _flat(origins)
-        own = None
-        if per_call:
-            own = {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
-                   "depth_sums": torch.zeros_like(self.depth_sums)}
+        own = self._own(per_call)
         if seg_lows and seg_target is not None:
-            for v in seg_lows:
-                _need_gpu(v, "seg_lows")
-                if v.shape[1] != self.num_classes:
-                    raise ValueError(f"Evaluator: {v.shape[1]} classes, built for {self.num_classes}")
-            lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
-            if lab.dtype not in _LAB_DTYPES:
-                lab = lab.long()
-            cm, ce = (own["cm"], own["ce_sums"]) if per_call else (self.cm, self.ce_sums)
-            E.slide_seg_update([v.detach().contiguous() for v in seg_lows], flat, wh, ww, lab.contiguous(),
-                               self.ignore_index, cm, ce, False)
-            if per_call:
-                self.cm += cm
-                self.ce_sums += ce
+            lows, lab, cm, ce = self._seg_args(seg_lows, "seg_lows", seg_target, own)
+            E.slide_seg_update(lows, flat, wh, ww, lab, self.ignore_index, cm, ce, False)
+            self._add_back(own, "cm", "ce_sums")
         if depth_lows and depth_target is not None:
-            for v in depth_lows:
-                _need_gpu(v, "depth_lows")
-            B = depth_target.shape[0]
-            tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
-            mk = None
-            if depth_mask is not None:
-                mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
-            sums = own["depth_sums"] if per_call else self.depth_sums
-            E.slide_depth_update([v.detach().contiguous() for v in depth_lows], flat, wh, ww, tg, mk, self.min_depth,
-                                 self.max_depth, self.clamp_pred, self.eps, sums, False)
-            if per_call:
-                self.depth_sums += sums
+            lows, tg, mk, sums = self._depth_args(depth_lows, "depth_lows", depth_target, depth_mask, own)
+            E.slide_depth_update(lows, flat, wh, ww, tg, mk, self.min_depth, self.max_depth, self.clamp_pred,
+                                 self.eps, sums, False)
+            self._add_back(own, "depth_sums")
         return own
 
     def update_view_windows(self, seg_lows=None, depth_lows=None, views=(), origins=(), seg_target=None,
@@ -482,37 +457,16 @@ class Evaluator:
         probs = _probs(average)
         E = _E()
         vflat, oflat = _flat(views), _flat(origins)
-        own = None
-        if per_call:
-            own = {"cm": torch.zeros_like(self.cm), "ce_sums": torch.zeros_like(self.ce_sums),
-                   "depth_sums": torch.zeros_like(self.depth_sums)}
+        own = self._own(per_call)
         if seg_lows and seg_target is not None:
-            for v in seg_lows:
-                _need_gpu(v, "seg_lows")
-                if v.shape[1] != self.num_classes:
-                    raise ValueError(f"Evaluator: {v.shape[1]} classes, built for {self.num_classes}")
-            lab = seg_target.reshape(seg_target.shape[0], *_hw(seg_target))
-            if lab.dtype not in _LAB_DTYPES:
-                lab = lab.long()
-            cm, ce = (own["cm"], own["ce_sums"]) if per_call else (self.cm, self.ce_sums)
-            E.slide_tta_seg_update([v.detach().contiguous() for v in seg_lows], vflat, oflat, lab.contiguous(),
-                                   self.ignore_index, probs, cm, ce, False)
-            if per_call:
-                self.cm += cm
-                self.ce_sums += ce
+            lows, lab, cm, ce = self._seg_args(seg_lows, "seg_lows", seg_target, own)
+            E.slide_tta_seg_update(lows, vflat, oflat, lab, self.ignore_index, probs, cm, ce, False)
+            self._add_back(own, "cm", "ce_sums")
         if depth_lows and depth_target is not None:
-            for v in depth_lows:
-                _need_gpu(v, "depth_lows")
-            B = depth_target.shape[0]
-            tg = depth_target.detach().reshape(B, *_hw(depth_target)).float().contiguous()
-            mk = None
-            if depth_mask is not None:
-                mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
-            sums = own["depth_sums"] if per_call else self.depth_sums
-            E.slide_tta_depth_update([v.detach().contiguous() for v in depth_lows], vflat, oflat, tg, mk,
-                                     self.min_depth, self.max_depth, self.clamp_pred, self.eps, sums, False)
-            if per_call:
-                self.depth_sums += sums
+            lows, tg, mk, sums = self._depth_args(depth_lows, "depth_lows", depth_target, depth_mask, own)
+            E.slide_tta_depth_update(lows, vflat, oflat, tg, mk, self.min_depth, self.max_depth, self.clamp_pred,
+                                     self.eps, sums, False)
+            self._add_back(own, "depth_sums")
         return own
 
     def all_reduce(self, group=None):
