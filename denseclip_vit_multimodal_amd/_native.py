@@ -104,6 +104,15 @@ _SIGS = {
                                 _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_upsample_eval_depth": [_i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
                                   _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    # any class count 1 <= K <= 256 (csrc/classes.hip): the signatures of the 19-class counterparts
+    "dclip_score_map_classes": [_c_void_p, _i32, _i64, _i64, _i64, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32,
+                                _f32, _c_void_p],
+    "dclip_upsample_ce_classes_ws_floats": [_i32, _i32, _i32, _i32],
+    "dclip_upsample_ce_classes": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
+                                  _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "dclip_upsample_eval_seg_classes_ws_bytes": [_i32, _i32, _i32, _i32],
+    "dclip_upsample_eval_seg_classes": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
+                                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "dclip_ensemble_eval_ws_bytes": [_i32, _i32, _i32],
     "dclip_ensemble_eval_seg": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
                                 _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
@@ -139,6 +148,7 @@ _SIGS = {
 }
 EXPORTED = sorted(list(_SIGS) + ["dclip_last_error", "dclip_abi_version"])
 ENSEMBLE_MAX_VIEWS = 16
+CLASSES_MAX = 256  # DCLIP_CLASSES_MAX: the widest class count of the *_classes entry points (csrc/classes.hip)
 
 
 class View(ctypes.Structure):
@@ -215,6 +225,8 @@ def load(path=None):
         lib.dclip_layernorm_bwd_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_eval_ws_bytes.restype = ctypes.c_int64
+        lib.dclip_upsample_ce_classes_ws_floats.restype = ctypes.c_int64
+        lib.dclip_upsample_eval_seg_classes_ws_bytes.restype = ctypes.c_int64
         lib.dclip_adamw_ws_bytes.restype = ctypes.c_int64
         lib.dclip_ensemble_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_slide_eval_ws_bytes.restype = ctypes.c_int64

@@ -308,6 +308,24 @@ def _register_fakes():
         B, H, W = target.shape
         return _e(B, 1, H, W, like=preds[0], dtype=f32) if want_up else None
 
+    # any class count up to 256 (csrc/classes.hip)
+    @reg("dclip_eval::upsample_argmax_classes")
+    def _(logits, H, W):
+        return _e(logits.shape[0], H, W, like=logits, dtype=torch.uint8)
+
+    @reg("dclip_eval::seg_update_classes")
+    def _(logits, labels, ignore_index, cm, ce_sums, want_pred, ws=None):
+        return _e(*labels.shape, like=logits, dtype=torch.uint8) if want_pred else None
+
+    @reg("dclip_classes::score_map")
+    def _(v, bstride, row_off, ld, text, B, HW, eps):
+        return _e(B, text.shape[1], HW, like=v, dtype=f32)
+
+    @reg("dclip_classes::upsample_ce")
+    def _(logits, labels, ignore_index):
+        return (_e(1, like=logits, dtype=torch.float64), _e(1, like=logits, dtype=torch.int32),
+                _e(*logits.shape, like=logits, dtype=f32))
+
     # dclip_optim::* — the native AdamW step (csrc/optim.hip), a namespace of its own
     @reg("dclip_optim::adamw_prepare")
     def _(desc, desc_host, grads, tiles, hp, found_inf, state, with_norm):

@@ -47,9 +47,30 @@ def model_kwargs(cfg, clip_path_override=None):
     return out
 
 
+def config_class_names(cfg, class_names=None):
+    """The model's class names: the argument, else the YAML's `data.class_names`, else the Cityscapes
+    names; `data.classes: N` must agree with their number, and so must `decode_head.num_classes`
+    (which DenseCLIP lets override the names' count).  Names outside the built-in token table need
+    DENSECLIP_BPE_PATH (utils.tokenize)."""
+    data = cfg.get("data") or {}
+    names = class_names if class_names is not None else data.get("class_names")
+    names = list(names) if names is not None else list(CITYSCAPES_CLASSES)
+    n = data.get("classes")
+    if n is not None and int(n) != len(names):
+        raise ValueError(f"config: data.classes is {n} but there are {len(names)} class names"
+                         + ("" if class_names is not None or data.get("class_names") is not None
+                            else " (the built-in Cityscapes names): give data.class_names"))
+    head = (cfg.get("model") or {}).get("decode_head") or {}
+    if head.get("num_classes") is not None and int(head["num_classes"]) != len(names):
+        raise ValueError(f"config: model.decode_head.num_classes is {head['num_classes']} but there are "
+                         f"{len(names)} class names")
+    return names
+
+
 def build_model(cfg, class_names=None, clip_path_override=None):
     from .denseclip import DenseCLIP
     kw = model_kwargs(cfg, clip_path_override)
+    class_names = config_class_names(cfg, class_names)
     if kw["clip_pretrained_path"] and not os.path.exists(kw["clip_pretrained_path"]):
         kw["clip_pretrained_path"] = None  # the reference logs and continues (denseclip.py:190)
-    return DenseCLIP(class_names=class_names or CITYSCAPES_CLASSES, **kw)
+    return DenseCLIP(class_names=class_names, **kw)

@@ -294,6 +294,101 @@ __device__ __forceinline__ void seg_score(const float (&v)[PX][K], const int* t,
     }
 }
 
+// The chunked form of seg_score, for a class count too wide for one thread's registers: the classes
+// arrive CK at a time, in ascending order, and SegRun carries what the scan needs between chunks:
+// the running (max, argmax) and, with labels, the running sum of exp(v - max) and the target's value.
+template <int PX>
+struct SegRun {
+    float m[PX], s[PX], vt[PX];
+    int a[PX];
+    __device__ __forceinline__ void reset() {
+#pragma unroll
+        for (int p = 0; p < PX; ++p) {
+            m[p] = -INFINITY;
+            s[p] = 0.f;
+            vt[p] = 0.f;
+            a[p] = 0;
+        }
+    }
+};
+
+// classes [k0, k0 + kc) of PX pixels, kc <= CK: a strict > keeps the lowest index among equal maxima,
+// within a chunk and across chunks; the sum is rescaled whenever the maximum moves (exp(-inf) = 0
+// covers the first chunk)
+template <int CK, int PX, bool LAB>
+__device__ __forceinline__ void seg_score_chunk(const float (&v)[PX][CK], int k0, int kc, const int* t,
+                                                SegRun<PX>& r) {
+#pragma unroll
+    for (int p = 0; p < PX; ++p) {
+        float m = r.m[p];
+        int a = r.a[p];
+#pragma unroll
+        for (int k = 0; k < CK; ++k)
+            if (k < kc && v[p][k] > m) {
+                m = v[p][k];
+                a = k0 + k;
+            }
+        r.a[p] = a;
+        if constexpr (LAB) {
+            const int tk = t[p] - k0;
+            float s = r.s[p] * __expf(r.m[p] - m), vt = r.vt[p];
+#pragma unroll
+            for (int k = 0; k < CK; ++k) {
+                if (k < kc) s += __expf(v[p][k] - m);
+                vt = k == tk ? v[p][k] : vt;
+            }
+            r.s[p] = s;
+            r.vt[p] = vt;
+        }
+        r.m[p] = m;
+    }
+}
+
+// after the last chunk: am[p], and with labels the CE terms in pixel order and the (target,
+// prediction) cells, one integer add per run of equal cells, into `hist` (K x K u32; LDS or global:
+// integer adds are exact in any order); nvalid += the pixels scored
+template <int PX, bool LAB>
+__device__ __forceinline__ void seg_score_finish(const SegRun<PX>& r, int K, const int* t, int n, int ignore,
+                                                 unsigned* __restrict__ hist, double& lsum, unsigned& nvalid,
+                                                 int (&am)[PX]) {
+    int cell_prev = -1;
+    unsigned run = 0;
+#pragma unroll
+    for (int p = 0; p < PX; ++p) {
+        am[p] = r.a[p];
+        if constexpr (LAB) {
+            const int tp = t[p];
+            const bool valid = p < n && tp != ignore && tp >= 0 && tp < K;  // ignore first: it may lie below K
+            if (valid) {
+                lsum += (double)(__logf(r.s[p]) - (r.vt[p] - r.m[p]));
+                ++nvalid;
+            }
+            const int cell = valid ? tp * K + r.a[p] : -1;
+            if (cell != cell_prev) {
+                if (cell_prev >= 0) atomicAdd(&hist[cell_prev], run);
+                cell_prev = cell;
+                run = 0;
+            }
+            ++run;
+        }
+    }
+    if constexpr (LAB) {
+        if (cell_prev >= 0) atomicAdd(&hist[cell_prev], run);
+    }
+}
+
+// stage_patch for the classes [k0, k0 + kc) of a K-class map alone
+template <typename TL>
+__device__ __forceinline__ void stage_patch_chunk(float* __restrict__ low_s, const TL* __restrict__ low, int b, int K,
+                                                  int k0, int kc, int h, int w, int ilo, int nr, int jlo, int nc,
+                                                  int nrow, int ncol) {
+    const int per = nr * nc;
+    for (int e = threadIdx.x; e < kc * per; e += blockDim.x) {
+        const int k = e / per, r = (e % per) / nc, c = e % nc;
+        low_s[(k * nrow + r) * ncol + c] = (float)low[(((int64_t)b * K + k0 + k) * h + ilo + r) * w + jlo + c];
+    }
+}
+
 // 4 class ids of one row; `vec`: the row segment is aligned for one dword
 __device__ __forceinline__ void store_pred4(uint8_t* __restrict__ pred, int64_t pix, int n, bool vec,
                                             const int (&am)[4]) {

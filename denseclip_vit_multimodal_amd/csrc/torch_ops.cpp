@@ -989,6 +989,97 @@ c10::optional<Tensor> depth_update(const Tensor& pred, const Tensor& target, con
     });
 }
 
+// ----------------------------------------------------------------------------- any class count (classes.hip)
+constexpr int64_t CLASSES_MAX = DCLIP_CLASSES_MAX;
+
+void check_classes(const char* op, const Tensor& logits) {
+    check_gpu(logits, "logits");
+    TORCH_CHECK(logits.dim() == 4, op, ": logits (B, K, h, w)");
+    TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kHalf ||
+                    logits.scalar_type() == at::kBFloat16, op, ": logits must be float32, float16 or bfloat16");
+    TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= CLASSES_MAX, op, ": K=", logits.size(1), " (1 <= K <= ",
+                CLASSES_MAX, " classes)");
+}
+
+// dclip::score_map for K <= 256
+Tensor score_map_classes(const Tensor& v, int64_t bstride, int64_t row_off, int64_t ld, const Tensor& text, int64_t B,
+                         int64_t HW, double eps) {
+    check_gpu(text, "text");
+    TORCH_CHECK(text.scalar_type() == at::kFloat && text.dim() == 3 && text.size(0) == B,
+                "score_map_classes: text (B, K, C) fp32");
+    const int64_t K = text.size(1), C = text.size(2);
+    TORCH_CHECK(K >= 1 && K <= CLASSES_MAX, "score_map_classes: K=", K, " (1 <= K <= ", CLASSES_MAX, " classes)");
+    TORCH_CHECK(v.scalar_type() == at::kHalf || v.scalar_type() == at::kBFloat16,
+                "score_map_classes: v must be float16 or bfloat16");
+    check_rows(v, bstride, row_off, ld, B, HW, C);
+    c10::DeviceGuard g(v.device());
+    Tensor out = at::empty({B, K, HW}, like(v, at::kFloat));
+    DCLIP_CALL(dclip_score_map_classes(v.data_ptr(), dt_code(v.scalar_type()), bstride, row_off, ld, ptr<float>(text),
+                                       ptr<float>(out), (int)B, (int)HW, (int)C, (int)K, (float)eps, stream_of(v)));
+    return out;
+}
+
+// dclip::upsample_ce for K <= 256: (loss sum f64[1], valid count i32[1], un-normalised low-res gradient f32)
+std::tuple<Tensor, Tensor, Tensor> upsample_ce_classes(const Tensor& logits, const Tensor& labels,
+                                                       int64_t ignore_index) {
+    check_classes("upsample_ce_classes", logits);
+    check_gpu(labels, "labels");
+    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == logits.size(0), "upsample_ce_classes: labels (B, H, W)");
+    c10::DeviceGuard g(logits.device());
+    const int B = (int)logits.size(0), K = (int)logits.size(1), h = (int)logits.size(2), w = (int)logits.size(3);
+    Tensor sums = at::zeros({1}, like(logits, at::kDouble));
+    Tensor cnt = at::zeros({1}, like(logits, at::kInt));
+    Tensor grad = at::zeros(logits.sizes(), like(logits, at::kFloat));
+    Tensor ws = at::empty({dclip_upsample_ce_classes_ws_floats(B, K, h, w)}, like(logits, at::kFloat));
+    DCLIP_CALL(dclip_upsample_ce_classes(dt_code(logits.scalar_type()), logits.data_ptr(), B, K, h, w,
+                                         labels.data_ptr(), lab_code(labels.scalar_type()), (int)labels.size(1),
+                                         (int)labels.size(2), (int)ignore_index, (double*)sums.data_ptr(),
+                                         (unsigned*)cnt.data_ptr(), ptr<float>(grad), ptr<float>(ws),
+                                         stream_of(logits)));
+    return {sums, cnt, grad};
+}
+
+// the bytes of seg_update_classes' workspace for these sizes
+int64_t seg_classes_ws_bytes(int64_t B, int64_t K, int64_t h, int64_t w) {
+    TORCH_CHECK(K >= 1 && K <= CLASSES_MAX, "seg_classes_ws_bytes: K=", K, " (1 <= K <= ", CLASSES_MAX, " classes)");
+    return dclip_upsample_eval_seg_classes_ws_bytes((int)B, (int)K, (int)h, (int)w);
+}
+
+// dclip_eval::upsample_argmax for K <= 256
+Tensor upsample_argmax_classes(const Tensor& logits, int64_t H, int64_t W) {
+    check_classes("upsample_argmax_classes", logits);
+    c10::DeviceGuard g(logits.device());
+    Tensor pred = at::empty({logits.size(0), H, W}, like(logits, at::kByte));
+    DCLIP_CALL(dclip_upsample_eval_seg_classes(dt_code(logits.scalar_type()), logits.data_ptr(), (int)logits.size(0),
+                                               (int)logits.size(1), (int)logits.size(2), (int)logits.size(3), nullptr,
+                                               0, (int)H, (int)W, 0, ptr<uint8_t>(pred), nullptr, nullptr, nullptr,
+                                               nullptr, stream_of(logits)));
+    return pred;
+}
+
+// dclip_eval::seg_update for K <= 256; ws: the caller's scratch (uint8, at least seg_classes_ws_bytes), or
+// none to allocate it here
+c10::optional<Tensor> seg_update_classes(const Tensor& logits, const Tensor& labels, int64_t ignore_index, Tensor& cm,
+                                         Tensor& ce_sums, bool want_pred, const c10::optional<Tensor>& ws) {
+    check_classes("seg_update_classes", logits);
+    check_opt(ws, "ws");
+    const int64_t need = dclip_upsample_eval_seg_classes_ws_bytes((int)logits.size(0), (int)logits.size(1),
+                                                                  (int)logits.size(2), (int)logits.size(3));
+    const bool has_ws = ws.has_value() && ws->defined();
+    TORCH_CHECK(!has_ws || (ws->scalar_type() == at::kByte && ws->numel() >= need), "seg_update_classes: ws must be "
+                "uint8 with at least ", need, " bytes");
+    return seg_update_with("seg_update_classes", logits, labels, cm, ce_sums, want_pred,
+                           [&](int H, int W, uint8_t* pred, unsigned long long* cnt) {
+        Tensor scratch = has_ws ? *ws : at::empty({need}, like(logits, at::kByte));
+        DCLIP_CALL(dclip_upsample_eval_seg_classes(dt_code(logits.scalar_type()), logits.data_ptr(),
+                                                   (int)logits.size(0), (int)logits.size(1), (int)logits.size(2),
+                                                   (int)logits.size(3), labels.data_ptr(),
+                                                   lab_code(labels.scalar_type()), H, W, (int)ignore_index, pred,
+                                                   ptr<int64_t>(cm), ptr<double>(ce_sums), cnt, scratch.data_ptr(),
+                                                   stream_of(logits)));
+    });
+}
+
 // ----------------------------------------------------------------------------- fused test-time ensembling
 // the host view table of dclip_ensemble_eval_* from the views' low-res maps (B, K, h, w) and flip flags
 std::vector<dclip_view> ensemble_views(at::TensorList maps, at::IntArrayRef flips, bool depth, const char* op) {
@@ -1468,9 +1559,27 @@ TORCH_LIBRARY(dclip_eval, m) {
     m.def("slide_tta_depth(Tensor[] preds, int[] views, int[] origins, int H, int W) -> Tensor");
     m.def("slide_tta_depth_update(Tensor[] preds, int[] views, int[] origins, Tensor target, Tensor? mask, "
           "float min_depth, float max_depth, bool clamp_pred, float eps, Tensor(a!) sums, bool want_up) -> Tensor?");
+    // upsample_argmax / seg_update for any class count up to 256 (classes.hip)
+    m.def("upsample_argmax_classes(Tensor logits, int H, int W) -> Tensor");
+    m.def("seg_update_classes(Tensor logits, Tensor labels, int ignore_index, Tensor(a!) cm, Tensor(b!) ce_sums, "
+          "bool want_pred, Tensor(c!)? ws=None) -> Tensor?");
+    m.def("seg_classes_ws_bytes(int B, int K, int h, int w) -> int", &seg_classes_ws_bytes);
+}
+
+// score_map / upsample_ce for any class count up to 256 (classes.hip), beside the pinned dclip:: set
+TORCH_LIBRARY(dclip_classes, m) {
+    m.def("score_map(Tensor v, int bstride, int row_off, int ld, Tensor text, int B, int HW, float eps) -> Tensor");
+    m.def("upsample_ce(Tensor logits, Tensor labels, int ignore_index) -> (Tensor, Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(dclip_classes, CUDA, m) {
+    m.impl("score_map", &score_map_classes);
+    m.impl("upsample_ce", &upsample_ce_classes);
 }
 
 TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
+    m.impl("upsample_argmax_classes", &upsample_argmax_classes);
+    m.impl("seg_update_classes", &seg_update_classes);
     m.impl("slide_tta_argmax", &slide_tta_argmax);
     m.impl("slide_tta_seg_update", &slide_tta_seg_update);
     m.impl("slide_tta_depth", &slide_tta_depth);

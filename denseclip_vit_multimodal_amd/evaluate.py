@@ -1,5 +1,5 @@
 """On-device validation: class maps, mIoU / pixel accuracy, depth errors and the validation losses,
-from the heads' low-res outputs, without materialising the resized (B, 19, H, W) logits.
+from the heads' low-res outputs, without materialising the resized (B, K, H, W) logits.
 
 The reference's validate() (train_denseclip.py:294-684) resizes both heads to the label size, then
 takes argmax -> confusion matrix / accuracy (denseclip/utils.py:109-139, compute_segmentation_metrics),
@@ -45,12 +45,29 @@ import torch
 import torch.nn.functional as F
 
 from . import _torch_ops
-from ._native import ENSEMBLE_MAX_VIEWS, SLIDE_MAX_WINDOWS, SLIDE_TTA_MAX_WINDOWS
+from ._native import CLASSES_MAX, ENSEMBLE_MAX_VIEWS, SLIDE_MAX_WINDOWS, SLIDE_TTA_MAX_WINDOWS
 
 DEPTH_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 TTA_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)  # the reference's --aug-test ratios (test.py:93-96)
 AVERAGES = ("logits", "probs")
 _LAB_DTYPES = (torch.int64, torch.int32, torch.uint8)
+CITYSCAPES_K = 19  # the class count of the register-resident kernels; any other K <= CLASSES_MAX is chunked
+
+
+def _check_classes(K, what):
+    """True when K takes the chunked kernels (csrc/classes.hip), False for the 19-class ones"""
+    K = int(K)
+    if K < 1 or K > CLASSES_MAX:
+        raise ValueError(f"{what}: {K} classes (the fused evaluation takes 1 to {CLASSES_MAX})")
+    return K != CITYSCAPES_K
+
+
+def _only_cityscapes(K, what):
+    """the ensemble / sliding-window kernels are built for 19 classes"""
+    if K is not None and int(K) != CITYSCAPES_K:
+        raise NotImplementedError(f"{what}: {int(K)} classes: the multi-scale / flip and sliding-window evaluation "
+                                  f"kernels are built for {CITYSCAPES_K} classes; only the plain path (predict, "
+                                  "Evaluator.update, validate without tta / slide) takes another class count")
 
 
 def _E():
@@ -72,6 +89,8 @@ def upsample_argmax(logits, size):
     """argmax over the classes of the bilinear (align_corners=False) resize of `logits` (B, K, h, w)
     to `size`: uint8 (B, H, W), the lowest class index among equal maxima (torch.argmax's rule)."""
     _need_gpu(logits, "logits")
+    if _check_classes(logits.shape[1], "upsample_argmax"):
+        return _E().upsample_argmax_classes(logits.detach().contiguous(), int(size[0]), int(size[1]))
     return _E().upsample_argmax(logits.detach().contiguous(), int(size[0]), int(size[1]))
 
 
@@ -132,8 +151,10 @@ def predict_tta(model, img, scales=TTA_SCALES, flip=True, average="logits", size
     (csrc/headensemble.hip: no per-view full-size tensor).  `average`: 'logits' or 'probs' for the
     class map (the depth is always the mean of the predictions)."""
     probs = _probs(average)
+    _only_cityscapes(getattr(model, "num_classes", None), "predict_tta")
     H, W = _hw(img) if size is None else (int(size[0]), int(size[1]))
     segs, depths, flips = forward_views(model, img, scales, flip)
+    _only_cityscapes(segs[0].shape[1] if segs else None, "predict_tta")
     E = _E()
     return {"seg": E.ensemble_argmax(segs, flips, H, W, probs) if segs else None,
             "depth": E.ensemble_depth(depths, flips, H, W) if depths else None}
@@ -228,8 +249,10 @@ def predict_slide(model, img, crop_size, stride, windows_per_forward=None):
     """`predict` under sliding-window inference (mmseg's test_cfg mode='slide'): {'seg': uint8
     (B, H, W), 'depth': fp32 (B, 1, H, W)} from the mean, over the windows that cover a pixel, of the
     windows' outputs resized to the window size (csrc/headslide.hip: no image-sized accumulator)."""
+    _only_cityscapes(getattr(model, "num_classes", None), "predict_slide")
     H, W = _hw(img)
     segs, depths, (wh, ww), origins = forward_windows(model, img, crop_size, stride, windows_per_forward)
+    _only_cityscapes(segs[0].shape[1] if segs else None, "predict_slide")
     E = _E()
     return {"seg": E.slide_argmax(segs, _flat(origins), wh, ww, H, W) if segs else None,
             "depth": E.slide_depth(depths, _flat(origins), wh, ww, H, W) if depths else None}
@@ -285,9 +308,11 @@ def predict_slide_tta(model, img, crop_size, stride, scales=TTA_SCALES, flip=Tru
     mirrored back (csrc/headslidetta.hip: no per-view tensor).  `average`: 'probs' (mmseg's rule) or
     'logits' for the class map; the depth is always the mean of the predictions."""
     probs = _probs(average)
+    _only_cityscapes(getattr(model, "num_classes", None), "predict_slide_tta")
     H, W = _hw(img)
     segs, depths, views, origins = forward_view_windows(model, img, crop_size, stride, scales, flip,
                                                         windows_per_forward)
+    _only_cityscapes(segs[0].shape[1] if segs else None, "predict_slide_tta")
     E = _E()
     return {"seg": E.slide_tta_argmax(segs, _flat(views), _flat(origins), H, W, probs) if segs else None,
             "depth": E.slide_tta_depth(depths, _flat(views), _flat(origins), H, W) if depths else None}
@@ -334,6 +359,8 @@ class Evaluator:
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.num_classes, self.ignore_index = int(num_classes), int(ignore_index)
+        self.chunked = _check_classes(self.num_classes, "Evaluator")  # K != 19: csrc/classes.hip
+        self._seg_ws = {}  # the chunked kernel's workspace per (device, bytes): allocated once, reused by every update
         self.min_depth, self.max_depth, self.clamp_pred = float(min_depth), float(max_depth), bool(clamp_pred)
         self.lambd, self.eps = float(lambd), float(eps)
         self.device = torch.device(device)
@@ -381,6 +408,15 @@ class Evaluator:
             mk = depth_mask.reshape(B, *_hw(depth_mask)).to(torch.uint8).contiguous()
         return [v.detach().contiguous() for v in maps], tg, mk, self.depth_sums if own is None else own["depth_sums"]
 
+    def _classes_ws(self, low):
+        """the chunked kernel's scratch for maps of this shape, sized by dclip_upsample_eval_seg_classes_ws_bytes"""
+        n = int(_E().seg_classes_ws_bytes(int(low.shape[0]), self.num_classes, int(low.shape[2]), int(low.shape[3])))
+        key = (low.device, n)  # images of many sizes (ADE20K's) share one buffer as long as the size agrees
+        ws = self._seg_ws.get(key)
+        if ws is None:
+            ws = self._seg_ws[key] = torch.empty(n, dtype=torch.uint8, device=low.device)
+        return ws
+
     def update(self, seg_lowres=None, depth_lowres=None, seg_target=None, depth_target=None, depth_mask=None,
                per_call=False):
         """Add one batch: `seg_lowres` (B, K, h, w) with `seg_target` (B, H, W) int64 / int32 / uint8,
@@ -391,7 +427,10 @@ class Evaluator:
         own = self._own(per_call)
         if seg_lowres is not None and seg_target is not None:
             (low,), lab, cm, ce = self._seg_args([seg_lowres], "seg_lowres", seg_target, own)
-            E.seg_update(low, lab, self.ignore_index, cm, ce, False)
+            if self.chunked:
+                E.seg_update_classes(low, lab, self.ignore_index, cm, ce, False, self._classes_ws(low))
+            else:
+                E.seg_update(low, lab, self.ignore_index, cm, ce, False)
             self._add_back(own, "cm", "ce_sums")
         if depth_lowres is not None and depth_target is not None:
             (low,), tg, mk, sums = self._depth_args([depth_lowres], "depth_lowres", depth_target, depth_mask, own)
@@ -408,6 +447,7 @@ class Evaluator:
         tensor besides the workspace, added to the running state; per_call=True returns the call's
         own sums."""
         probs = _probs(average)
+        _only_cityscapes(self.num_classes, "Evaluator.update_views")
         E = _E()
         flips = [int(f) for f in flips]
         own = self._own(per_call)
@@ -430,6 +470,7 @@ class Evaluator:
         pixel, of the windows' outputs resized to (wh, ww).  Same contract as `update`: no host
         synchronisation, no new tensor besides the workspace, added to the running state;
         per_call=True returns the call's own sums."""
+        _only_cityscapes(self.num_classes, "Evaluator.update_windows")
         E = _E()
         wh, ww = int(window_size[0]), int(window_size[1])
         flat = _flat(origins)
@@ -455,6 +496,7 @@ class Evaluator:
         synchronisation, no new tensor besides the workspace, added to the running state;
         per_call=True returns the call's own sums."""
         probs = _probs(average)
+        _only_cityscapes(self.num_classes, "Evaluator.update_view_windows")
         E = _E()
         vflat, oflat = _flat(views), _flat(origins)
         own = self._own(per_call)
@@ -554,6 +596,8 @@ def validate(model, batches, evaluator=None, tta=None, slide=None, slide_tta=Non
         with torch.no_grad():
             for img, seg, depth, mask in batches:
                 if evaluator is None:
+                    if "num_classes" not in loss_cfg and getattr(model, "num_classes", None):
+                        loss_cfg["num_classes"] = int(model.num_classes)
                     evaluator = Evaluator(device=img.device, **loss_cfg)
                 if slide_tta is not None:
                     segs, depths, views, origins = forward_view_windows(model, img, **slide_tta)

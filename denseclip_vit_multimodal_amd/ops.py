@@ -112,6 +112,15 @@ class _TimedOps:
         return call
 
 
+from ._native import CLASSES_MAX  # noqa: E402  the widest class count of the fused score map / CE / evaluation
+
+
+def DC():
+    """torch.ops.dclip_classes: score_map / upsample_ce for a class count the 19-class kernels refuse"""
+    D()
+    return torch.ops.dclip_classes
+
+
 def D():
     """torch.ops.dclip (loads libdclip_torch.so on first use; raises if it is missing)."""
     global _D
@@ -505,7 +514,13 @@ def score_map(v, text, B, HW, row_off=0, bstride=None, eps=1e-12):
     _check(text)
     C = v.shape[-1]
     bstride = HW * C if bstride is None else bstride
-    return D().score_map(v, bstride, row_off, C, text, B, HW, float(eps))
+    K = text.shape[1]
+    if K <= 32:
+        return D().score_map(v, bstride, row_off, C, text, B, HW, float(eps))
+    if K > CLASSES_MAX:
+        raise ValueError(f"score_map: {K} classes (the fused kernels take at most {CLASSES_MAX})")
+    _stat("score_map_classes")
+    return DC().score_map(v, bstride, row_off, C, text, B, HW, float(eps))
 
 
 def score_concat(tgt, score):
@@ -1730,8 +1745,14 @@ class UpsampleCEFn(torch.autograd.Function):
         _check(lg, lab)
         if lab.dtype not in _LAB_DT:
             lab = lab.long()
+        if K > CLASSES_MAX:
+            raise ValueError(f"UpsampleCEFn: {K} classes (the fused kernels take at most {CLASSES_MAX})")
         e0 = _tic()
-        sums, cnt, grad = D().upsample_ce(lg, lab, int(ignore_index))
+        if K == 19:
+            sums, cnt, grad = D().upsample_ce(lg, lab, int(ignore_index))
+        else:  # any other class count: the chunked kernel (csrc/classes.hip)
+            _stat("upsample_ce_classes")
+            sums, cnt, grad = DC().upsample_ce(lg, lab, int(ignore_index))
         _toc("upsample_ce", e0)
         n = cnt.to(torch.float64).clamp(min=1)
         ctx.save_for_backward(grad, n)

@@ -59,7 +59,7 @@ class CapturedEval:
     graph: `forward_lowres`, the fused upsample + argmax of the logits and the resize of the depth.
     Calling it copies `img` in, replays and returns the captured {'seg': uint8 (B, H, W) class map,
     'depth': fp32 (B, 1, H, W)} (the SAME tensors every call, as CapturedForward's).  The resized
-    (B, 19, H, W) logits are never materialised, so the graph's pool does not hold them either."""
+    (B, K, H, W) logits are never materialised, so the graph's pool does not hold them either."""
 
     def __init__(self, model, example, size=None, warmup=2):
         from . import evaluate

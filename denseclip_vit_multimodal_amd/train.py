@@ -752,15 +752,16 @@ class CapturedTrainStep:
             if len(batch) != self.accum_steps:
                 raise ValueError(f"CapturedTrainStep: accum_steps={accum_steps} needs that many micro-batches "
                                  f"(got {len(batch)})")
-            if not all(t.is_cuda for mb in batch for t in mb):
+            if not all(t.is_cuda for mb in batch for t in mb if t is not None):
                 raise RuntimeError("CapturedTrainStep: GPU batch tensors only (no CPU fallback)")
-            self.micro = [[t.detach().clone() for t in mb] for mb in batch]
+            self.micro = [[None if t is None else t.detach().clone() for t in mb] for mb in batch]
             self.static = [t for mb in self.micro for t in mb]
             step_fn, first = train_step_accum, self.micro
         else:
-            if not all(t.is_cuda for t in batch):
+            # a seg-only model's batch has no depth target / mask: (img, seg, None, None)
+            if not all(t.is_cuda for t in batch if t is not None):
                 raise RuntimeError("CapturedTrainStep: GPU batch tensors only (no CPU fallback)")
-            self.static = [t.detach().clone() for t in batch]
+            self.static = [None if t is None else t.detach().clone() for t in batch]
             step_fn, first = train_step, self.static
         args = (silog, seg_weight, silog_weight)
         m = _unwrap(model)
@@ -768,7 +769,7 @@ class CapturedTrainStep:
         if saved is not None:
             m.graph_text = "side"  # the text path as a forked branch of this capture (no nested graph)
         try:
-            dev = self.static[0].device
+            dev = next(t for t in self.static if t is not None).device
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
@@ -787,6 +788,10 @@ class CapturedTrainStep:
             if self.accum_steps > 1:
                 batch = [t for mb in batch for t in mb]
             for s, t in zip(self.static, batch):
+                if s is None and t is None:
+                    continue
+                if s is None or t is None:
+                    raise ValueError("CapturedTrainStep was captured with other batch entries absent (None)")
                 if s.shape != t.shape or s.dtype != t.dtype:
                     raise ValueError(f"CapturedTrainStep was captured for {tuple(s.shape)} {s.dtype}, "
                                      f"got {tuple(t.shape)} {t.dtype}")

@@ -45,6 +45,7 @@
  *   dclip_row_mean             F.adaptive_avg_pool2d(...,(1,1)) denseclip.py:596
  *   dclip_score_map            F.normalize x2 + einsum('bchw,bkc->bkhw')
  *                              denseclip.py:672-675
+ *   dclip_*_classes            the score map, fused CE and fused evaluation for any class count <= 256
  *   dclip_score_concat         upsample + torch.cat of the score map onto a read-out map
  *                              denseclip.py:684-694
  *   dclip_bilinear_fwd/bwd     F.interpolate(bilinear, align_corners=False)
@@ -416,6 +417,35 @@ int dclip_upsample_eval_seg(int low_dt, const void* logits, int B, int K, int h,
 int dclip_upsample_eval_depth(int low_dt, const void* pred, int B, int h, int w, const float* target,
                               const uint8_t* mask, int H, int W, float min_depth, float max_depth, int clamp_pred,
                               float eps, float* up, double* sums, void* ws, void* stream);
+
+/* The three fused paths above for any class count 1 <= K <= DCLIP_CLASSES_MAX = 256 (csrc/classes.hip; additive to ABI 7).
+ * The 19-class entry points keep a pixel's K values in registers and the K-channel patch in LDS; these
+ * walk the classes in chunks of 16, so neither grows with K.  Arguments and semantics are those of the
+ * counterpart unless noted; any other K is rejected before a launch.
+ *   dclip_score_map_classes:  dclip_score_map with the class embeddings in 32-row tiles: the same
+ *       normalisation, eps rule (an all-zero pixel row scores 0), strided rows and fixed-order norms.
+ *   dclip_upsample_ce_classes:  dclip_upsample_ce.  ignore_index is tested before the range [0, K), so
+ *       K = 256 with ignore 255 skips the label 255.  An int64 label that no int32 holds is out of range.
+ *       ws: dclip_upsample_ce_classes_ws_floats(B, K, h, w) floats, 8-byte aligned, contents undefined
+ *       on entry; at most 3x the gradient's bytes + 1 MiB wherever K * w >= 4 (below that the 16
+ *       bytes of loss partials per low-res row and 32-column chunk weigh more than the gradient
+ *       itself: 6x at K = w = 1).  No atomics; bitwise reproducible.
+ *   dclip_upsample_eval_seg_classes:  dclip_upsample_eval_seg (pred u8, so a class id is at most 255).
+ *       ws: dclip_upsample_eval_seg_classes_ws_bytes(B, K, h, w) bytes (<= 80 MiB), 8-byte aligned,
+ *       contents undefined on entry.  The confusion counts are added to u32 histograms in ws with integer
+ *       atomics (exact in any order); the CE sum has f32 terms summed in f64 in a fixed order: two runs
+ *       are bitwise equal.                                                                            */
+#define DCLIP_CLASSES_MAX 256
+int dclip_score_map_classes(const void* v, int v_dt, int64_t bstride, int64_t row_off, int64_t ld, const float* t,
+                            float* score, int B, int HW, int C, int K, float eps, void* stream);
+int64_t dclip_upsample_ce_classes_ws_floats(int B, int K, int h, int w);
+int dclip_upsample_ce_classes(int low_dt, const void* logits, int B, int K, int h, int w, const void* labels,
+                              int lab_dt, int H, int W, int ignore_index, double* loss_sum, unsigned* count,
+                              float* grad, float* ws, void* stream);
+int64_t dclip_upsample_eval_seg_classes_ws_bytes(int B, int K, int h, int w);
+int dclip_upsample_eval_seg_classes(int low_dt, const void* logits, int B, int K, int h, int w, const void* labels,
+                                    int lab_dt, int H, int W, int ignore_index, uint8_t* pred, int64_t* cm,
+                                    double* loss_sum, unsigned long long* count, void* ws, void* stream);
 
 /* Multi-scale + flip test-time ensembling fused into the evaluation above (the reference's aug_test,
  * denseclip.py:1005-1041 with test.py:91-96, without materialising one resized tensor per view).
