@@ -2459,7 +2459,7 @@ void fwd_launch(const void* qkv, void* o, float* lse, int B, int N, int H, hipSt
 // partial last blocks and zero-filled tails)
 template <typename T>
 bool bwd2_launch(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                 int N, int H, float scale, hipStream_t st, void* f8ws = nullptr) {
+                 int N, int H, float scale, hipStream_t st, void* f8ws = nullptr, void* seam = nullptr) {
     if (N < 257 || dclip_option(DCLIP_OPT_ATTN_BWD_KERNEL) == 1) return false;
     // a ragged N - 1 (partial last query / key blocks, masked tails) in the default passes only
     const bool ragged = (N - 1) % 256 != 0;
@@ -2479,7 +2479,8 @@ bool bwd2_launch(const void* qkv, const void* o, const void* dout, const float* 
         // key 0's terms), one key-major sweep for dK, dV and per-key-block dQ partials, the ordered dQ
         // reduction; then the CLS row's merge as the two-pass path (-3 % per launch, -1.1 % per train
         // step against dq2 + dkdv6, profiles/r06/r6z, r6w).  Workspace past the two-pass part: dS_q0
-        // (B*H*N floats), then the partials (attn_bwd1_part_bytes, 256-B aligned)
+        // (B*H*N floats), then the partials (attn_bwd1_part_bytes, 256-B aligned).  seam: the persistent
+        // sweep's state (dclip_attn_bwd keeps it at the workspace's start)
         const int64_t bhn = (int64_t)B * H * N;
         float* ds0v = nstat + 2 * bhn;
         void* part = (void*)(((uintptr_t)(ds0v + bhn) + 255) & ~(uintptr_t)255);
@@ -2487,7 +2488,7 @@ bool bwd2_launch(const void* qkv, const void* o, const void* dout, const float* 
         float* r0kv = ws0;
         float* r0q = ws0 + (int64_t)B * H * nqp * 128;
         attn_bwd1_launch(std::is_same<T, bf16>::value ? DCLIP_BF16 : DCLIP_F16, qkv, o, dout, lse, delta, nstat, ds0v,
-                         r0kv, r0q, part, dqkv, B, N, H, scale, st);
+                         r0kv, r0q, part, dqkv, B, N, H, scale, st, seam);
         attn_bwd_row0_fold_merge<T><<<B * H, 64, 0, st>>>((const T*)qkv, (const T*)dout, lse, delta, r0kv, nqp, r0q, nkb,
                                                           (T*)dqkv, N, H, scale, 1.0f / LOG2E);
         return true;
@@ -2556,8 +2557,8 @@ bool bwd2_launch(const void* qkv, const void* o, const void* dout, const float* 
 
 template <typename T>
 void bwd_launch(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
-                int B, int N, int H, float scale, hipStream_t st, void* f8ws = nullptr) {
-    if (bwd2_launch<T>(qkv, o, dout, lse, delta, dqkv, B, N, H, scale, st, f8ws)) return;
+                int B, int N, int H, float scale, hipStream_t st, void* f8ws = nullptr, void* seam = nullptr) {
+    if (bwd2_launch<T>(qkv, o, dout, lse, delta, dqkv, B, N, H, scale, st, f8ws, seam)) return;
     // dQ (w.r.t. the unscaled q) = dZ K scale;  dK = dZ^T q scale = dZ^T q' / log2(e)
     if (dclip_option(DCLIP_OPT_ATTN_DQ_WAVES) == 4) {
         dim3 grid(((N + 127) / 128) * B * H);
@@ -2623,11 +2624,13 @@ static int64_t bwd_ws_two_pass(int B, int N, int H) {
 }
 
 // Independent of every option (a size queried under one option serves a launch under any other):
-// for N >= 257 the one-pass backward's (the largest form: + dS_q0 (B*H*N) + the dQ partials), below
-// it the two-pass part alone
+// for N >= 257 the one-pass backward's (the largest form: the persistent sweep's seam state at the
+// start, + dS_q0 (B*H*N) + the dQ partials), below it the two-pass part alone
 extern "C" int64_t dclip_attn_bwd_workspace(int B, int N, int H) {
     const int64_t two_pass = bwd_ws_two_pass(B, N, H);
-    if (N >= 257) return two_pass + (int64_t)B * H * N + (attn_bwd1_part_bytes(B, N, H) + 3) / 4 + 64;
+    if (N >= 257)
+        return attn_bwd1_state_bytes(B, N, H) / 4 + two_pass + (int64_t)B * H * N +
+               (attn_bwd1_part_bytes(B, N, H) + 3) / 4 + 64;
     return two_pass;
 }
 
@@ -2651,8 +2654,15 @@ extern "C" int dclip_attn_bwd(int dt, const void* qkv, const void* o, const void
                      "dclip_attn_bwd: N too large for the one-pass backward's dQ partials (N = %d; "
                      "DCLIP_OPT_ATTN_BWD_BLOCK 6 selects the two-pass backward)", N);
     hipStream_t st = (hipStream_t)stream;
-    if (dt == DCLIP_BF16) bwd_launch<bf16>(qkv, o, dout, lse, delta_ws, dqkv, B, N, H, scale, st);
-    else bwd_launch<f16>(qkv, o, dout, lse, delta_ws, dqkv, B, N, H, scale, st);
+    // N >= 257: the seam state of the one-pass backward's persistent sweep first (a block of its own at
+    // the allocation's start, a multiple of 256 B: what the launch zeroes), every other part behind it
+    void* seam = nullptr;
+    if (N >= 257) {
+        seam = delta_ws;
+        delta_ws += attn_bwd1_state_bytes(B, N, H) / 4;
+    }
+    if (dt == DCLIP_BF16) bwd_launch<bf16>(qkv, o, dout, lse, delta_ws, dqkv, B, N, H, scale, st, nullptr, seam);
+    else bwd_launch<f16>(qkv, o, dout, lse, delta_ws, dqkv, B, N, H, scale, st, nullptr, seam);
     DCLIP_LAUNCH_CHECK();
     return 0;
 }

@@ -22,6 +22,13 @@
 //                              stored as a 16-bit partial per (key block, query)
 //   3. attn_bwd1_dq_reduce     dQ[q] = sum over key blocks of the partials, in block order, + the key-0
 //                              term dS_q0 k_0 — deterministic, no atomics
+// The default sweep (option 0) is persistent (attn_bwd1p_kernel: one workgroup per CU walks the tiles)
+// and does most of step 3 itself: at a seam between two tiles a workgroup reduces its share of the
+// (image, head)s it walked a round or two earlier — the same arithmetic (dq_reduce_rows), so the
+// same bits — if their tiles are all published (a counter per (image, head), agent-scope
+// release / acquire; it never waits), while other CUs run MFMAs.  Step 3 then is the completion pass:
+// it skips the 32-row blocks a seam has done and reduces the rest (the last rounds, anything a seam
+// found incomplete).  Option 10 keeps a workgroup per tile and the whole reduction in step 3.
 //
 // The dS^T image is [256 keys][64 queries] 16-bit with an 8-byte-unit XOR swizzle
 // (ds_unit_swz): conflict-free for both its writers (ds_write_b64 of 4 consecutive queries of one
@@ -94,8 +101,8 @@ __device__ __forceinline__ typename Mfma<T>::frag trds_frag(const char* __restri
 // = queries 16s + 8(j>>1) + 4h + 2(j&1) + {0, 1}) into the dS^T image: four 8-byte stores of four
 // consecutive queries.  dsw = (key row * 128 + 8 (h ^ ds_unit_swz(row))) of block 0; block 1's rows
 // are 32 further (same swizzle), i.e. + 4 KiB
-__device__ __forceinline__ uint32_t ds_put_base(int wave) {
-    const int lane = threadIdx.x & 63, row = wave * 64 + (lane & 31);
+__device__ __forceinline__ uint32_t ds_put_base(int wave, int lane) {
+    const int row = wave * 64 + (lane & 31);
     return (uint32_t)(row * 128 + 8 * ((lane >> 5) ^ ds_unit_swz(row)));
 }
 template <int SUB, int KB>
@@ -161,7 +168,7 @@ __device__ __forceinline__ void sub1(K6<T>& k, int h, int l32, int lane, const c
     load_qg<T>(qa, ga, nb, nsub, l32, h);
     fence();
     // ---- R4
-    const uint32_t dsw = ds_put_base(wave);
+    const uint32_t dsw = ds_put_base(wave, lane);
     ds_put<SUB, 0>(dsimg, dsw, k0.d);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -455,6 +462,89 @@ __global__ __launch_bounds__(256, 1) void attn_bwd1_kernel(const T* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------- dQ reduce (shared arithmetic)
+// dQ[q] = sum_j part_j[q] (key blocks in order) + dS_q0 k_0 scale / DsScale for R blocks of 32 query
+// rows rb .. rb + R - 1 of (image, head) bh (the first nr of them; queries 1..N-1): 8 lanes per row
+// (8 columns each), the R rows of a lane in flight together.  The arithmetic of a row does not depend
+// on R: attn_bwd1_dq_reduce (R = 1) and the sweep's seam duty (R = DUTY_R) give the same bits.
+template <typename T, int R>
+__device__ __forceinline__ void dq_reduce_rows(const T* dqpart, const float* __restrict__ ds0v,
+                                               const T* __restrict__ qkv, T* __restrict__ dqkv, int N, int H, int nkb,
+                                               int bh, int rb, int nr, float sc, int tid) {
+    typedef T t8 __attribute__((ext_vector_type(8)));
+    const int b = bh / H, hd = bh % H;
+    const int c8 = (tid & 7) * 8;
+    const int C = H * HD;
+    const int64_t ld = 3 * (int64_t)C;
+    const int64_t Np = 1 + 64 * (int64_t)((N - 1 + 63) / 64);
+    const t8 kv = *(const t8*)(qkv + (int64_t)b * N * ld + C + hd * HD + c8);
+    // bf16 partials are unscaled (store_dq_half): the key-0 term joins them unscaled and the sum is
+    // scaled once (sc is a power of two, so this equals scaling every term)
+    constexpr bool unscaled = std::is_same<T, bf16>::value;
+    int q[R];
+    bool ok[R];
+    const T* p[R];
+    float acc[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        q[r] = 1 + (rb + r) * 32 + (tid >> 3);
+        ok[r] = r < nr && q[r] < N;
+        const int qc = ok[r] ? q[r] : 1;  // a row that is not this call's computes on query 1 and stores nothing
+        const float w = ds0v[(int64_t)bh * N + qc] * (unscaled ? 1.0f : sc);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            acc[r][e] = w * (float)kv[e];
+            asm volatile("" : "+v"(acc[r][e]));  // the product rounded on its own (no FMA with the first partial)
+        }
+        p[r] = dqpart + ((int64_t)bh * Np + qc) * nkb * 64 + c8;  // this query's nkb partials, adjacent
+    }
+    // the partials are read as global (not flat) loads, all 8 R of a step issued before the first add
+    // (inside the sweep the scheduler, short of registers, would otherwise wait for each on its own)
+    typedef __attribute__((address_space(1))) const t8 gt8;
+    int j = 0;
+    for (; j + 8 <= nkb; j += 8) {
+        t8 v[R][8];
+        fence();
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[r][u] = __builtin_nontemporal_load((gt8*)(p[r] + (j + u) * 64));
+        fence();
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[r][e] += (float)v[r][u][e];
+    }
+    for (; j < nkb; ++j) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const t8 v = __builtin_nontemporal_load((gt8*)(p[r] + j * 64));
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[r][e] += (float)v[e];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (!ok[r]) continue;
+        t8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (T)(unscaled ? acc[r][e] * sc : acc[r][e]);
+        *(t8*)(dqkv + ((int64_t)b * N + q[r]) * ld + hd * HD + c8) = o;
+    }
+}
+
+// The persistent sweep's seam state, zeroed by the launcher in every call: done[nbh] (tiles of an
+// (image, head) whose partials are published), then reduced[nbh][nrb] (32-row blocks of dQ a seam duty
+// has written: the completion pass skips them), nrb = ceil((N - 1) / 32)
+typedef __attribute__((address_space(1))) unsigned gu32;
+constexpr int DUTY_R = 4;
+constexpr int DUTY_PERIOD = 2;  // <= 31 (a bit per owed seam)
+__host__ __device__ inline int64_t bwd1b_reduced_at(int nbh, int bh, int nrb, int rb) {
+    return nbh + (int64_t)bh * nrb + rb;
+}
+
 // ---------------------------------------------------------------------------- the pipelined sweep (default)
 // attn_bwd1b_kernel: attn_bwd1_kernel's arithmetic (dK / dV bit for bit; dQ the same products summed
 // in the same per-tile order) with the slice's dQ^T tile taken OFF its own barrier: the dS^T image is
@@ -591,7 +681,7 @@ __device__ __forceinline__ void sub2(K6<T>& k, int h, int l32, int lane, int wav
     fence();
     // ---- R4
     dq_load2<T, 8 * SUB + 6>(dbf, dsprev, dqo);
-    const uint32_t dsw = ds_put_base(wave);
+    const uint32_t dsw = ds_put_base(wave, lane);
     ds_put<SUB, 0>(dscur, dsw, k0.d);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -653,14 +743,33 @@ __device__ __forceinline__ void dq_tile_kt(f32x16& acc, const typename Mfma<T>::
     }
 }
 
+// the persistent sweep's arguments as the kernel-argument segment holds them: what only a seam needs is
+// read from there at the seam instead of being held in (spilled) SGPRs across the sweep's loop
 template <typename T>
-__global__ __launch_bounds__(256, 1) void attn_bwd1b_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
-                                                            const float* __restrict__ lse,
-                                                            const float* __restrict__ delta,
-                                                            const float* __restrict__ nlse,
-                                                            const float* __restrict__ ndelta, T* __restrict__ dqkv,
-                                                            T* __restrict__ dqpart, int N, int H, float dk_scale,
-                                                            float scale, float* __restrict__ r0q) {
+struct B1pArgs {
+    const T *qkv, *dout;
+    const float *lse, *delta, *nlse, *ndelta;
+    T *dqkv, *dqpart;
+    int N, H;
+    float dk_scale, scale;
+    float* r0q;
+    int tiles, nbh;        // B*H*nkb, B*H
+    int period;            // seams between a workgroup's duty batches (DUTY_PERIOD; 0: no duties)
+    unsigned* state;       // done / reduced (bwd1b_reduced_at)
+    const float* ds0v;
+};
+
+// One tile (key block kblk of (image, head) bh = tile / nkb) of the sweep; returns bh.  P: the
+// persistent form's seam work (state: bwd1b_reduced_at): the tile's partials published on done[bh],
+// then the duties owed for the last `pend` seams (0: none now) — for the seam after tile
+// u = tile - j G, share u % nkb of the (image, head) walked at u - G, if that one is complete
+template <typename T, bool P>
+__device__ __forceinline__ int bwd1b_tile(const T* __restrict__ qkv, const T* __restrict__ dout,
+                                          const float* __restrict__ lse, const float* __restrict__ delta,
+                                          const float* __restrict__ nlse, const float* __restrict__ ndelta,
+                                          T* __restrict__ dqkv, T* __restrict__ dqpart, int N, int H, float dk_scale,
+                                          float scale, float* __restrict__ r0q, int tile, int pend, int wave,
+                                          __attribute__((address_space(4))) const B1pArgs<T>* ka) {
     constexpr int NW = B1_NW, KB = B1_KB;
     typedef Dkv2Ctx<T, NW> X;
     typedef typename Mfma<T>::frag frag;
@@ -673,12 +782,16 @@ __global__ __launch_bounds__(256, 1) void attn_bwd1b_kernel(const T* __restrict_
     X c;
     K6<T> k;
     c.smem = smem;
-    c.lane = threadIdx.x & 63;
-    c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // P: the lane id read per tile through an opaque asm (and the wave index, found once, passed
+    // through one), so nothing derived from them is hoisted out of the tile walk and held (spilled)
+    // across the sweep's loop, and threadIdx.x is not live in it beside the lane id; the same for the
+    // scalars derived from N and H
+    c.lane = P ? lane_now() : (int)(threadIdx.x & 63);
+    c.wave = P ? wave : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if constexpr (P) asm volatile("" : "+s"(N), "+s"(H), "+s"(c.wave));
     c.h = c.lane >> 5;
     c.l32 = c.lane & 31;
     const int nkb = (N - 1 + KB - 1) / KB;
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
     const int kblk = tile % nkb, bh = tile / nkb, b = bh / H, hd = bh % H;
     const int C = H * HD;
     const int64_t ld = 3 * (int64_t)C;
@@ -823,17 +936,51 @@ __global__ __launch_bounds__(256, 1) void attn_bwd1b_kernel(const T* __restrict_
     dq_settle(dq);
     store_dq_half<T>(out.part, out.rs, (uint32_t)(64 * (c.nt - 1) + 1 + out.qb * 32), out.db, dq, out.sc);
     wait_vmcnt<0>();
-    if (r0q != nullptr) {
+    unsigned duty = 0;
+    if (r0q != nullptr) {  // always, when P
         // CLS-row fold (dkdv6's)
         __syncthreads();
-        const int lane = __lane_id();
+        const int lane = P ? lane_now() : (int)__lane_id();
+        float* part = (float*)(smem + NW * 64 * 128);
+        gu32* state = nullptr;
+        if constexpr (P) {
+            asm volatile("" : "+s"(ka));
+            state = (gu32*)ka->state;
+            // every wave's partial stores are drained (the vmcnt(0) above) and behind the barrier: one
+            // lane (of the last wave: wave 0 has the fold's final sum) publishes the tile with an
+            // agent-scope release and the counter add, then asks once (never again) whether the
+            // (image, head) of the previous tile is complete; the answer goes to every wave through
+            // an idle ring word behind the fold's second barrier
+            if (c.wave == NW - 1 && lane == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __hip_atomic_fetch_add(state + bh, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                // bit j: the (image, head) walked at tile - (j + 1) G is complete (j < pend: the seams
+                // whose duty is still owed)
+                unsigned ready = 0;
+                for (int j = 0; j < pend; ++j) {
+                    const int u = tile - (j + 1) * (int)gridDim.x;
+                    if (u >= 0 && __hip_atomic_load(state + u / nkb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+                                      (unsigned)nkb)
+                        ready |= 1u << j;
+                }
+                ((unsigned*)part)[NW * 64] = ready;
+            }
+        }
         char* img = smem + c.wave * 64 * 128;
         r0_put<T>(img, k.kf[0], lane & 31, lane >> 5);
         r0_put<T>(img, k.kf[1], 32 + (lane & 31), lane >> 5);
         const float aq = r0_colsum<T, 64>(img, (const float*)(smem + B2_RING) + c.wave * 64, lane);
-        float* part = (float*)(smem + NW * 64 * 128);
         part[c.wave * 64 + lane] = aq;
         __syncthreads();
+        if constexpr (P) {
+            duty = __builtin_amdgcn_readfirstlane(((const unsigned*)part)[NW * 64]);  // workgroup-uniform
+            // the acquire (one lane's, its wait ahead of the barrier before the duty's loads)
+            if (duty && c.wave == NW - 1 && lane == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
         if (c.wave == 0) {
             float sum = 0.f;
 #pragma unroll
@@ -851,6 +998,75 @@ __global__ __launch_bounds__(256, 1) void attn_bwd1b_kernel(const T* __restrict_
             store_row_t21<T>(rk, k.dk[kb], dk_scale / DsScale<T>::v, c.h);
             store_row_t21<T>(rk + C, k.dv[kb], 1.0f, c.h);
         }
+    }
+    if constexpr (P) {
+        if (duty) {
+            // the duty owed since the seam after tile u = tile - j G: share u % nkb of the (image, head)
+            // walked at u - G, i.e. ceil(nrb / nkb) blocks of 32 query rows, DUTY_R at a time (their
+            // loads in flight together), in attn_bwd1_dq_reduce's arithmetic; the dK / dV stores above
+            // drain meanwhile
+            __syncthreads();  // the acquire is complete
+            asm volatile("" : "+s"(ka));  // no load of the partials is moved above the barrier
+            const T* pp = ka->dqpart;
+            const int nrb = (N - 1 + 31) / 32, per = (nrb + nkb - 1) / nkb;
+            const int tid = c.wave * 64 + lane_now();
+            for (int j = 0; j < pend; ++j) {
+                if (!(duty >> j & 1)) continue;
+                const int u = tile - j * (int)gridDim.x, pbh = (u - (int)gridDim.x) / nkb, share = u % nkb;
+                const int rb1 = min((share + 1) * per, nrb);
+                for (int rb = share * per; rb < rb1; rb += DUTY_R) {
+                    const int nr = min(DUTY_R, rb1 - rb);
+                    dq_reduce_rows<T, DUTY_R>(pp, ka->ds0v, ka->qkv, ka->dqkv, N, H, nkb, pbh, rb, nr,
+                                              ka->scale / DsScale<T>::v, tid);
+                    if (tid < nr)
+                        __hip_atomic_store((gu32*)ka->state + bwd1b_reduced_at(ka->nbh, pbh, nrb, rb + tid), 1u,
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+        // the next tile's prologue writes the LDS this fold read
+        __syncthreads();
+    }
+    return bh;
+}
+
+// today's launch form (DCLIP_OPT_ATTN_BWD_BLOCK 10, and whenever every tile gets a workgroup of its
+// own): one workgroup per tile
+template <typename T>
+__global__ __launch_bounds__(256, 1) void attn_bwd1b_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
+                                                            const float* __restrict__ lse,
+                                                            const float* __restrict__ delta,
+                                                            const float* __restrict__ nlse,
+                                                            const float* __restrict__ ndelta, T* __restrict__ dqkv,
+                                                            T* __restrict__ dqpart, int N, int H, float dk_scale,
+                                                            float scale, float* __restrict__ r0q) {
+    bwd1b_tile<T, false>(qkv, dout, lse, delta, nlse, ndelta, dqkv, dqpart, N, H, dk_scale, scale, r0q,
+                         xcd_remap(blockIdx.x, gridDim.x), 0, 0, nullptr);
+}
+
+// the persistent form (the default): G = gridDim.x workgroups, at most one per CU, each walking tiles
+// round * G + xcd_remap(block, G) — the key blocks of an (image, head) still run together on one
+// XCD — and owing, for the seam after each tile, the reduction of its share of the (image, head) it
+// walked a round earlier, done if that one's tiles are all published (bwd1b_tile; never a wait: what
+// a seam finds incomplete, and the last round, is left to the completion pass attn_bwd1_dq_reduce)
+template <typename T>
+__global__ __launch_bounds__(256, 1) void attn_bwd1p_kernel(const B1pArgs<T> args) {
+    typedef __attribute__((address_space(4))) const B1pArgs<T> kargs_t;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // a workgroup takes its duties in batches, every `period` seams and after its last tile, the
+    // workgroups of an XCD in `period` phases: at any seam most CUs go straight on with MFMAs while
+    // the others stream partials (all CUs streaming at every seam is the separate pass's HBM-bound time
+    // again, only inside the sweep)
+    const int period = args.period;
+    int owed = 0, round = blockIdx.x / 8;
+    for (int tile = xcd_remap(blockIdx.x, gridDim.x); tile < args.tiles; tile += gridDim.x, ++round) {
+        kargs_t* ka = (kargs_t*)__builtin_amdgcn_kernarg_segment_ptr();  // args, where the dispatch put them
+        asm volatile("" : "+s"(ka));
+        ++owed;
+        const bool now = period > 0 && (round % period == period - 1 || tile + (int)gridDim.x >= ka->tiles);
+        bwd1b_tile<T, true>(ka->qkv, ka->dout, ka->lse, ka->delta, ka->nlse, ka->ndelta, ka->dqkv, ka->dqpart, ka->N,
+                            ka->H, ka->dk_scale, ka->scale, ka->r0q, tile, now ? owed : 0, wave, ka);
+        if (now || period <= 0) owed = 0;
     }
 }
 
@@ -954,42 +1170,13 @@ __global__ __launch_bounds__(256) void attn_bwd1_prep_kernel(const T* __restrict
 template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd1_dq_reduce(const T* __restrict__ dqpart, const float* __restrict__ ds0v,
                                                            const T* __restrict__ qkv, T* __restrict__ dqkv, int N, int H,
-                                                           int nkb, int nrb, float sc) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    const int rb = blockIdx.x % nrb, bh = blockIdx.x / nrb, b = bh / H, hd = bh % H;
-    const int q = 1 + rb * 32 + (threadIdx.x >> 3), c8 = (threadIdx.x & 7) * 8;
-    if (q >= N) return;
-    const int C = H * HD;
-    const int64_t ld = 3 * (int64_t)C;
-    const int64_t Np = 1 + 64 * (int64_t)((N - 1 + 63) / 64);
-    const t8 kv = *(const t8*)(qkv + (int64_t)b * N * ld + C + hd * HD + c8);
-    // bf16 partials are unscaled (store_dq_half): the key-0 term joins them unscaled and the sum is
-    // scaled once (sc is a power of two, so this equals scaling every term)
-    constexpr bool unscaled = std::is_same<T, bf16>::value;
-    const float w = ds0v[(int64_t)bh * N + q] * (unscaled ? 1.0f : sc);
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = w * (float)kv[e];
-    const T* p = dqpart + ((int64_t)bh * Np + q) * nkb * 64 + c8;  // this query's nkb partials, adjacent
-    int j = 0;
-    for (; j + 8 <= nkb; j += 8) {
-        t8 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load((const t8*)(p + (j + u) * 64));
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += (float)v[u][e];
-    }
-    for (; j < nkb; ++j) {
-        const t8 v = __builtin_nontemporal_load((const t8*)(p + j * 64));
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
-    }
-    t8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (T)(unscaled ? acc[e] * sc : acc[e]);
-    *(t8*)(dqkv + ((int64_t)b * N + q) * ld + hd * HD + c8) = r;
+                                                           int nkb, int nrb, float sc, const unsigned* state) {
+    const int rb = blockIdx.x % nrb, bh = blockIdx.x / nrb;
+    // the completion pass of the persistent sweep: a block a seam duty has reduced is done
+    if (state != nullptr && __hip_atomic_load((const gu32*)state + bwd1b_reduced_at(gridDim.x / nrb, bh, nrb, rb),
+                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+        return;
+    dq_reduce_rows<T, 1>(dqpart, ds0v, qkv, dqkv, N, H, nkb, bh, rb, 1, sc, threadIdx.x);
 }
 
 // the same sum (option DCLIP_OPT_ATTN_DQ_REDUCE 1): a workgroup takes 8 queries, whose partial runs
@@ -1003,11 +1190,17 @@ template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd1_dq_reduce_lds(const T* __restrict__ dqpart,
                                                                const float* __restrict__ ds0v,
                                                                const T* __restrict__ qkv, T* __restrict__ dqkv,
-                                                               int N, int H, int nkb, int nrb, float sc) {
+                                                               int N, int H, int nkb, int nrb, float sc,
+                                                               const unsigned* state) {
     typedef T t2 __attribute__((ext_vector_type(2)));
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) char rq_lds[];
     const int rb = blockIdx.x % nrb, bh = blockIdx.x / nrb, b = bh / H, hd = bh % H;
+    // the completion pass of the persistent sweep: the 32-row block of these 8 queries is done
+    if (state != nullptr &&
+        __hip_atomic_load((const gu32*)state + bwd1b_reduced_at(gridDim.x / nrb, bh, (N - 1 + 31) / 32, rb / (32 / RQ_Q)),
+                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+        return;
     const int q0 = 1 + rb * RQ_Q;
     const int C = H * HD;
     const int64_t ld = 3 * (int64_t)C;
@@ -1040,15 +1233,35 @@ __global__ __launch_bounds__(256) void attn_bwd1_dq_reduce_lds(const T* __restri
     *(t2*)(dqkv + ((int64_t)b * N + q) * ld + hd * HD + 2 * cp) = r;
 }
 
+int bwd1_cu_count() {
+    int dev = 0, c = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
+        c = 256;
+    return c;
+}
+
 template <typename T>
 void bwd1_launch(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, float* nstat,
                  float* ds0v, float* r0kv, int nqp, float* r0q, void* dqpart, void* dqkv, int B, int N, int H,
-                 float scale, hipStream_t st) {
-    const int nkb = (N - 1 + B1_KB - 1) / B1_KB;
+                 float scale, unsigned* state, hipStream_t st) {
+    const int nkb = (N - 1 + B1_KB - 1) / B1_KB, tiles = B * H * nkb;
     attn_bwd1_prep_kernel<T><<<B * H * nqp, 256, 0, st>>>((const T*)qkv, (const T*)o, (const T*)dout, lse, delta, nstat,
                                                           ds0v, r0kv, N, H, nqp,
                                                           dclip_option(DCLIP_OPT_ATTN_PREP_ORDER) == 1);
-    if (dclip_option(DCLIP_OPT_ATTN_BWD_BLOCK) != 9)  // the pipelined sweep (default); 9: the barrier form
+    // the persistent sweep (option 0) when it has seams: more tiles than workgroups (the CU count, or
+    // DCLIP_OPT_ATTN_BWD_WGS); its seam state zeroed in every call (a replayed graph starts clean)
+    const int blk = dclip_option(DCLIP_OPT_ATTN_BWD_BLOCK), cap = dclip_option(DCLIP_OPT_ATTN_BWD_WGS);
+    const int G = cap > 0 ? cap : bwd1_cu_count();
+    const bool persistent = blk == 0 && state != nullptr && r0q != nullptr && tiles > G;
+    if (!persistent) state = nullptr;
+    if (persistent) {
+        (void)hipMemsetAsync(state, 0, (size_t)attn_bwd1_state_bytes(B, N, H), st);  // a failure: the caller's launch check
+        const B1pArgs<T> args = {(const T*)qkv, (const T*)dout, lse,   delta,  nstat, nstat + (int64_t)B * H * N,
+                                 (T*)dqkv,      (T*)dqpart,     N,     H,      1.0f / LOG2E, scale,
+                                 r0q,           tiles,          B * H, DUTY_PERIOD, state, ds0v};
+        attn_bwd1p_kernel<T><<<G, 256, 0, st>>>(args);
+    } else if (blk != 9)  // the pipelined sweep, a workgroup per tile; 9: the barrier form
         attn_bwd1b_kernel<T><<<B * H * nkb, 256, 0, st>>>((const T*)qkv, (const T*)dout, lse, delta, nstat,
                                                           nstat + (int64_t)B * H * N, (T*)dqkv, (T*)dqpart, N, H,
                                                           1.0f / LOG2E, scale, r0q);
@@ -1059,12 +1272,12 @@ void bwd1_launch(const void* qkv, const void* o, const void* dout, const float* 
     if (dclip_option(DCLIP_OPT_ATTN_DQ_REDUCE) == 1 && nkb <= RQ_MAX_NKB) {
         const int nrb = (N - 1 + RQ_Q - 1) / RQ_Q;
         attn_bwd1_dq_reduce_lds<T><<<B * H * nrb, 256, RQ_Q * (nkb * 128 + 128), st>>>(
-            (const T*)dqpart, ds0v, (const T*)qkv, (T*)dqkv, N, H, nkb, nrb, scale / DsScale<T>::v);
+            (const T*)dqpart, ds0v, (const T*)qkv, (T*)dqkv, N, H, nkb, nrb, scale / DsScale<T>::v, state);
         return;
     }
     const int nrb = (N - 1 + 31) / 32;
     attn_bwd1_dq_reduce<T><<<B * H * nrb, 256, 0, st>>>((const T*)dqpart, ds0v, (const T*)qkv, (T*)dqkv, N, H, nkb, nrb,
-                                                        scale / DsScale<T>::v);
+                                                        scale / DsScale<T>::v, state);
 }
 
 }  // namespace
@@ -1076,12 +1289,21 @@ int64_t attn_bwd1_part_bytes(int B, int N, int H) {
     return (int64_t)B * H * nkb * np * 128;
 }
 
+// done[B*H] + reduced[B*H][ceil((N-1)/32)] words, padded to 256 B (what follows it in the workspace
+// keeps its alignment; the launcher's memset covers exactly this block)
+int64_t attn_bwd1_state_bytes(int B, int N, int H) {
+    const int64_t words = (int64_t)B * H * (1 + (N - 1 + 31) / 32);
+    return (words * 4 + 255) / 256 * 256;
+}
+
 void attn_bwd1_launch(int dt, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
                       float* nstat, float* ds0v, float* r0kv, float* r0q, void* dqpart, void* dqkv, int B, int N,
-                      int H, float scale, hipStream_t st) {
+                      int H, float scale, hipStream_t st, void* state) {
     const int nqp = attn_bwd1_prep_blocks(N);
     if (dt == DCLIP_BF16)
-        bwd1_launch<bf16>(qkv, o, dout, lse, delta, nstat, ds0v, r0kv, nqp, r0q, dqpart, dqkv, B, N, H, scale, st);
+        bwd1_launch<bf16>(qkv, o, dout, lse, delta, nstat, ds0v, r0kv, nqp, r0q, dqpart, dqkv, B, N, H, scale,
+                          (unsigned*)state, st);
     else
-        bwd1_launch<f16>(qkv, o, dout, lse, delta, nstat, ds0v, r0kv, nqp, r0q, dqpart, dqkv, B, N, H, scale, st);
+        bwd1_launch<f16>(qkv, o, dout, lse, delta, nstat, ds0v, r0kv, nqp, r0q, dqpart, dqkv, B, N, H, scale,
+                         (unsigned*)state, st);
 }

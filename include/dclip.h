@@ -96,7 +96,7 @@ int dclip_abi_version(void);
 #define DCLIP_OPT_ATTN_DKDV_QS 5     /* dK/dV pass query rows per barrier: 64 (default) or 128 */
 #define DCLIP_OPT_ATTN_BWD_KERNEL 7  /* 0 (default): CLS-split passes for N >= 257 (a ragged N-1 with the default pass variants only); 1: generic */
 #define DCLIP_OPT_ATTN_FWD_KERNEL 6  /* 0 (default): CLS-split kernels (the pipelined attn_fwd3 when N - 1 is a multiple of 256, else attn_fwd2, ragged N-1 included); 1: generic; 2: attn_fwd3 4 waves x 64 rows; 3: attn_fwd3 8 waves; 4: attn_fwd2 always */
-#define DCLIP_OPT_ATTN_BWD_BLOCK 8   /* CLS-split backward: 0 (default, round 6) / 10: the one-pass backward (attention_bwd1.hip: dK, dV and per-key-block dQ partials in one pipelined key-major sweep, an ordered dQ reduction; dclip_attn_bwd_workspace includes the partials, 3.2 GB at B=8, N=8193, H=12); 9: its unpipelined sweep; 6: the two-pass dQ + dK/dV passes, 64 keys per wave, AGPR dK / dV (attention_dkdv6.hip); 7: its software-pipelined schedule; 8: its ring DMA inside R4; 5: software-pipelined 32 keys per wave; 1: the unpipelined one */
+#define DCLIP_OPT_ATTN_BWD_BLOCK 8   /* CLS-split backward: 0 (default): the one-pass backward (attention_bwd1.hip: dK, dV and per-key-block dQ partials in one pipelined key-major sweep, an ordered dQ reduction; dclip_attn_bwd_workspace includes the partials, 3.2 GB at B=8, N=8193, H=12) with a persistent sweep (one workgroup per CU) that reduces most dQ partials at its tile seams, the reduction pass completing the rest; 10: the same with a workgroup per tile and the whole reduction in its own pass (bitwise equal); 9: the unpipelined sweep (a workgroup per tile); 6: the two-pass dQ + dK/dV passes, 64 keys per wave, AGPR dK / dV (attention_dkdv6.hip); 7: its software-pipelined schedule; 8: its ring DMA inside R4; 5: software-pipelined 32 keys per wave; 1: the unpipelined one */
 #define DCLIP_OPT_GEMM_TN_COLSUM 9   /* 0 (default): the 256x256 weight-gradient kernel sums dY's columns (bias gradient) itself; 1: a separate pass */
 #define DCLIP_OPT_GEMM_EPI 10      /* persistent NT GEMM epilogue: 0 (default) row-major through LDS, whole 128-B lines per store, streaming (nontemporal) stores for the wide forward outputs (N >= 2048, not RESIDUAL / GELU_BWD); 1 the accumulator-layout stores (16 rows x 64 B); 2 row-major, streaming stores for every output; 3 row-major, no streaming stores */
 #define DCLIP_OPT_GEMM_TAIL 11     /* persistent NT GEMM M tail (<= 16 rows): 0 (default) one latency-shaped MFMA launch (16 columns per workgroup, every K-slice load issued up front, side inputs prefetched); 1 the 256-row split-K tile + combine pair; 2 round 4's one launch (64 columns per workgroup, 8 waves, K % 256 == 0) */
@@ -108,7 +108,8 @@ int dclip_abi_version(void);
 #define DCLIP_OPT_GEMM_KLOOP 17     /* 8-wave GEMM K-loops: 0 (default) the persistent NT kernel with its fragment reads issued one 8-MFMA group ahead except on the GELU epilogue, the TN kernel as compiled; 1 read-ahead in every NT and TN K-loop; 2 none */
 #define DCLIP_OPT_ATTN_DQ_REDUCE 18 /* one-pass backward dQ reduction: 0 (default) 8 lanes per query, each lane its 8 columns over the key blocks; 1 8 queries per workgroup, their partial runs read contiguously into LDS (1 KiB per wave-instruction), then 2 columns per lane summed in the same key-block order (bitwise equal) */
 #define DCLIP_OPT_ATTN_PREP_ORDER 19 /* one-pass backward prep pass: 0 (default) query blocks of one head on adjacent workgroups; 1 the heads of one query block on adjacent workgroups (same per-workgroup work, bitwise equal) */
-#define DCLIP_OPT_COUNT 20
+#define DCLIP_OPT_ATTN_BWD_WGS 20 /* one-pass backward, persistent sweep (DCLIP_OPT_ATTN_BWD_BLOCK 0): its workgroup count; 0 (default) one per CU; a small value makes a small shape walk several rounds (tests). At or above the tile count (B*H*ceil((N-1)/256)) the sweep has no seams and runs a workgroup per tile */
+#define DCLIP_OPT_COUNT 21
 int dclip_set_option(int id, int value);
 
 /* LayerNorm over the last dim (cols), eps, affine w/b (fp32).  y = (x-mu)*rstd*w+b.
@@ -213,9 +214,12 @@ int dclip_attn_fwd(int dt, const void* qkv, void* o, float* lse,
  * of (B, N, H) alone — no option changes it, so a size queried once serves a launch under any
  * option: for N >= 257 it includes the one-pass form's partials (B*H*ceil((N-1)/256)*
  * (1+64*ceil((N-1)/64))*128 bytes, 3.2 GB at B = 8, N = 8193, H = 12), the largest form; below 257
- * it is the two-pass part alone.  Its contents on entry are irrelevant.  Its
- * first B*H*N floats receive delta; the rest holds the CLS-split row-0 partials, the negated lse /
- * delta planes, key 0's dS column and the dQ partials.  The one-pass form addresses an (image,
+ * it is the two-pass part alone.  Its contents on entry are irrelevant.  For N >= 257 it begins with
+ * the persistent sweep's seam state (B*H counters of published tiles, then B*H*ceil((N-1)/32) flags
+ * of reduced 32-row dQ blocks, 32-bit words, padded to 256 bytes), which every call that uses it
+ * zeroes itself with a memset node on `stream` (a captured call replays clean).  The next
+ * B*H*N floats (the first, below N = 257) receive delta; the rest holds the CLS-split row-0 partials,
+ * the negated lse / delta planes, key 0's dS column and the dQ partials.  The one-pass form addresses an (image,
  * head)'s partials with 32-bit offsets: when (1+64*ceil((N-1)/64))*ceil((N-1)/256)*128 >= 2^32
  * (N above about 92.7k) the call fails with DCLIP_ERR_ARG ("N too large") before any launch;
  * DCLIP_OPT_ATTN_BWD_BLOCK 6 (the two-pass backward) has no such limit.
