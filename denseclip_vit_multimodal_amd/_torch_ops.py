@@ -326,6 +326,13 @@ def _register_fakes():
         return (_e(1, like=logits, dtype=torch.float64), _e(1, like=logits, dtype=torch.int32),
                 _e(*logits.shape, like=logits, dtype=f32))
 
+    # the fused resize + CE with F.cross_entropy's other arguments (csrc/celossopt.hip)
+    @reg("dclip_loss::upsample_ce")
+    def _(logits, labels, ignore_index, class_weight, label_smoothing, pixel_weight, want_pixel_loss, want_grad):
+        return (_e(2, like=logits, dtype=torch.float64), _e(1, like=logits, dtype=torch.int32),
+                _e(*logits.shape, like=logits, dtype=f32) if want_grad else None,
+                _e(*labels.shape, like=logits, dtype=f32) if want_pixel_loss else None)
+
     # dclip_optim::* — the native AdamW step (csrc/optim.hip), a namespace of its own
     @reg("dclip_optim::adamw_prepare")
     def _(desc, desc_host, grads, tiles, hp, found_inf, state, with_norm):

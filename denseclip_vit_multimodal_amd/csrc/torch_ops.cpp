@@ -1039,6 +1039,44 @@ std::tuple<Tensor, Tensor, Tensor> upsample_ce_classes(const Tensor& logits, con
     return {sums, cnt, grad};
 }
 
+// dclip_loss::upsample_ce: the fused resize + CE with F.cross_entropy's other arguments (celossopt.hip), any
+// K <= 256: (sums f64[2] = (sum q l, sum q w_t), valid count i32[1], un-normalised low-res gradient f32 or
+// none, per-pixel loss f32 (B, H, W) or none)
+std::tuple<Tensor, Tensor, c10::optional<Tensor>, c10::optional<Tensor>> upsample_ce_opt(
+    const Tensor& logits, const Tensor& labels, int64_t ignore_index, const c10::optional<Tensor>& class_weight,
+    double label_smoothing, const c10::optional<Tensor>& pixel_weight, bool want_pixel_loss, bool want_grad) {
+    check_classes("dclip_loss::upsample_ce", logits);
+    check_gpu(labels, "labels");
+    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == logits.size(0), "dclip_loss::upsample_ce: labels (B, H, W)");
+    TORCH_CHECK(labels.device() == logits.device(), "dclip_loss::upsample_ce: labels on another device");
+    const int B = (int)logits.size(0), K = (int)logits.size(1), h = (int)logits.size(2), w = (int)logits.size(3);
+    check_vec(class_weight, K, "class_weight");
+    if (pixel_weight.has_value() && pixel_weight->defined()) {
+        check_gpu(*pixel_weight, "pixel_weight");
+        TORCH_CHECK(pixel_weight->scalar_type() == at::kFloat, "dclip: pixel_weight must be float32 (got ",
+                    pixel_weight->scalar_type(), ")");
+        TORCH_CHECK(pixel_weight->sizes() == labels.sizes(), "dclip: pixel_weight must have the labels' shape (B, H, W)");
+        TORCH_CHECK(pixel_weight->device() == logits.device(), "dclip: pixel_weight on another device");
+    }
+    if (class_weight.has_value() && class_weight->defined())
+        TORCH_CHECK(class_weight->device() == logits.device(), "dclip: class_weight on another device");
+    TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "dclip_loss::upsample_ce: label_smoothing=",
+                label_smoothing, " (0 <= label_smoothing < 1)");
+    c10::DeviceGuard g(logits.device());
+    Tensor sums = at::zeros({2}, like(logits, at::kDouble));
+    Tensor cnt = at::zeros({1}, like(logits, at::kInt));
+    Tensor grad = want_grad ? at::zeros(logits.sizes(), like(logits, at::kFloat)) : Tensor();
+    Tensor pl = want_pixel_loss ? at::empty(labels.sizes(), like(logits, at::kFloat)) : Tensor();
+    Tensor ws = at::empty({dclip_upsample_ce_opt_ws_floats(B, K, h, w)}, like(logits, at::kFloat));
+    DCLIP_CALL(dclip_upsample_ce_opt(dt_code(logits.scalar_type()), logits.data_ptr(), B, K, h, w, labels.data_ptr(),
+                                     lab_code(labels.scalar_type()), (int)labels.size(1), (int)labels.size(2),
+                                     (int)ignore_index, optr<const float>(class_weight), (float)label_smoothing,
+                                     optr<const float>(pixel_weight), ptr<float>(pl), (double*)sums.data_ptr(),
+                                     (unsigned*)cnt.data_ptr(), ptr<float>(grad), ptr<float>(ws), stream_of(logits)));
+    return {sums, cnt, want_grad ? c10::optional<Tensor>(grad) : c10::nullopt,
+            want_pixel_loss ? c10::optional<Tensor>(pl) : c10::nullopt};
+}
+
 // the bytes of seg_update_classes' workspace for these sizes
 int64_t seg_classes_ws_bytes(int64_t B, int64_t K, int64_t h, int64_t w) {
     TORCH_CHECK(K >= 1 && K <= CLASSES_MAX, "seg_classes_ws_bytes: K=", K, " (1 <= K <= ", CLASSES_MAX, " classes)");
@@ -1576,6 +1614,15 @@ TORCH_LIBRARY_IMPL(dclip_classes, CUDA, m) {
     m.impl("score_map", &score_map_classes);
     m.impl("upsample_ce", &upsample_ce_classes);
 }
+
+// the fused resize + CE with class weights, label smoothing, pixel weights and the per-pixel loss (celossopt.hip)
+TORCH_LIBRARY(dclip_loss, m) {
+    m.def("upsample_ce(Tensor logits, Tensor labels, int ignore_index, Tensor? class_weight, float label_smoothing, "
+          "Tensor? pixel_weight, bool want_pixel_loss, bool want_grad) -> "
+          "(Tensor sums, Tensor count, Tensor? grad, Tensor? pixel_loss)");
+}
+
+TORCH_LIBRARY_IMPL(dclip_loss, CUDA, m) { m.impl("upsample_ce", &upsample_ce_opt); }
 
 TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
     m.impl("upsample_argmax_classes", &upsample_argmax_classes);

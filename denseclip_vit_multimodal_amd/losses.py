@@ -1,6 +1,8 @@
-"""SILog depth loss (reference seg/denseclip/losses.py:7-78)."""
+"""SILog depth loss (reference seg/denseclip/losses.py:7-78) and the segmentation cross-entropy with
+class weights, label smoothing and online hard example mining."""
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 
 class SILogLoss(nn.Module):
@@ -28,3 +30,82 @@ class SILogLoss(nn.Module):
         Tf = T.to(d.dtype).clamp(min=1)
         loss = (d ** 2).sum() / Tf - self.lambd * d.sum() ** 2 / Tf ** 2
         return torch.where(T > 0, loss, torch.zeros_like(loss))
+
+
+def ohem_keep(p_t, valid, thresh, batch_kept):
+    """The keep mask of online hard example mining (mmseg's OHEMPixelSampler rule): with p_t the
+    softmax probability of the target at every pixel and `valid` the pixels that have one,
+        threshold = max(sorted_ascending(p_t[valid])[min(batch_kept, n_valid - 1)], thresh)
+    and a pixel is kept iff it is valid and p_t < threshold.  Everything stays on p_t's device:
+    the invalid pixels sort last (+inf) and the index is clamped with the device-side count, so
+    there is no host synchronisation.  No valid pixel: nothing is kept."""
+    flat = torch.where(valid, p_t, torch.full_like(p_t, float("inf"))).reshape(-1)
+    idx = torch.clamp(valid.sum() - 1, min=0, max=int(batch_kept))
+    kth = torch.sort(flat).values.gather(0, idx.reshape(1))
+    threshold = torch.clamp(kth, min=float(thresh))
+    return valid & (p_t < threshold)
+
+
+class SegCrossEntropy(nn.Module):
+    """The segmentation loss with the options people train with: class weights, label smoothing
+    and OHEM (ohem = dict(thresh=0.7, min_kept=100000): the loss is averaged over the pixels
+    `ohem_keep` keeps, min_kept per image).
+
+    forward(up_logits, labels) is the materialised formulation on logits already at the label
+    size: F.cross_entropy with the same arguments, the OHEM rule in torch; it runs anywhere.
+    fused(lowres_logits, labels) is the same loss from the low-res logits through
+    ops.upsample_cross_entropy: the resized logits never exist."""
+
+    def __init__(self, weight=None, label_smoothing=0.0, ignore_index=255, ohem=None):
+        super().__init__()
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f"SegCrossEntropy: label_smoothing={label_smoothing} (0 <= label_smoothing < 1)")
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).clone())
+        self.label_smoothing = float(label_smoothing)
+        self.ignore_index = int(ignore_index)
+        self.ohem = None
+        if ohem is not None:
+            self.ohem = {"thresh": float(ohem.get("thresh", 0.7)), "min_kept": int(ohem.get("min_kept", 100000))}
+            if not 0.0 < self.ohem["thresh"] <= 1.0 or self.ohem["min_kept"] < 0:
+                raise ValueError(f"SegCrossEntropy: ohem={ohem} (0 < thresh <= 1, min_kept >= 0)")
+
+    def _weight_on(self, device):
+        """the class weights where the logits are; the module itself stays where its owner put it (place it
+        with .to(device) beforehand: a copy made here costs a transfer per call and cannot be captured)"""
+        w = self.weight
+        return w if w is None or w.device == device else w.to(device)
+
+    def _valid(self, labels, K):
+        return (labels != self.ignore_index) & (labels >= 0) & (labels < K)
+
+    def forward(self, up_logits, labels):
+        w = self._weight_on(up_logits.device)
+        labels = labels.long()
+        if self.ohem is None:
+            return F.cross_entropy(up_logits, labels, weight=w, ignore_index=self.ignore_index,
+                                   label_smoothing=self.label_smoothing)
+        K = up_logits.shape[1]
+        valid = self._valid(labels, K)
+        t = torch.where(valid, labels, torch.zeros_like(labels))
+        with torch.no_grad():
+            x = up_logits.detach()  # selected in the logits' own precision, fp32 at the least
+            x = x.float() if x.dtype in (torch.float16, torch.bfloat16) else x
+            p_t = F.softmax(x, dim=1).gather(1, t[:, None]).squeeze(1)
+            keep = ohem_keep(p_t, valid, self.ohem["thresh"], self.ohem["min_kept"] * labels.shape[0])
+        l = F.cross_entropy(up_logits, labels, weight=w, ignore_index=self.ignore_index,
+                            label_smoothing=self.label_smoothing, reduction="none")
+        q = keep.to(l.dtype)
+        w_t = q if w is None else q * w.to(l.dtype)[t]
+        return (l * q).sum() / w_t.sum()
+
+    def fused(self, lowres_logits, labels):
+        from . import ops
+        w = self._weight_on(lowres_logits.device)
+        if self.ohem is None:
+            return ops.upsample_cross_entropy(lowres_logits, labels, self.ignore_index, w, self.label_smoothing)
+        with torch.no_grad():  # the selection: the plain per-pixel loss, forward only
+            nll = ops.upsample_cross_entropy(lowres_logits.detach(), labels, self.ignore_index, reduction="none")
+            keep = ohem_keep(torch.exp(-nll), self._valid(labels, lowres_logits.shape[1]), self.ohem["thresh"],
+                             self.ohem["min_kept"] * labels.shape[0])
+        return ops.upsample_cross_entropy(lowres_logits, labels, self.ignore_index, w, self.label_smoothing,
+                                          pixel_weight=keep.to(torch.float32))

@@ -121,6 +121,12 @@ def DC():
     return torch.ops.dclip_classes
 
 
+def DL():
+    """torch.ops.dclip_loss: the fused resize + CE with class weights, label smoothing and pixel weights"""
+    D()
+    return torch.ops.dclip_loss
+
+
 def D():
     """torch.ops.dclip (loads libdclip_torch.so on first use; raises if it is missing)."""
     global _D
@@ -1766,6 +1772,101 @@ class UpsampleCEFn(torch.autograd.Function):
         grad, n = ctx.saved_tensors
         d = grad * (g.to(torch.float64) / n).to(torch.float32)
         return d.to(ctx.in_dtype), None, None
+
+
+def _ce_opt_args(name, logits, labels, weight, pixel_weight):
+    """The contiguous, checked tensors dclip_loss::upsample_ce takes (f32 weights on the logits' device)"""
+    K = logits.shape[1]
+    lg = logits.detach().contiguous()
+    lab = labels.contiguous()
+    _check(lg, lab)
+    if lab.dtype not in _LAB_DT:
+        lab = lab.long()
+    if K > CLASSES_MAX:
+        raise ValueError(f"{name}: {K} classes (the fused kernels take at most {CLASSES_MAX})")
+    if weight is not None:
+        weight = weight.detach().to(device=lg.device, dtype=torch.float32).contiguous()
+    if pixel_weight is not None:
+        pixel_weight = pixel_weight.detach().to(device=lg.device, dtype=torch.float32).contiguous()
+    return lg, lab, weight, pixel_weight
+
+
+class UpsampleCEOptFn(torch.autograd.Function):
+    """F.cross_entropy(F.interpolate(logits, (H, W), bilinear, align_corners=False), labels, weight,
+    ignore_index, label_smoothing, reduction "mean" or "sum") with an optional per-pixel weight q
+    (mean = sum q l / sum q w_t), in one pass over the labels that also produces the low-res
+    gradient (csrc/celossopt.hip); backward scales it, as UpsampleCEFn does."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, weight, label_smoothing, pixel_weight, reduction):
+        lg, lab, cw, pw = _ce_opt_args("UpsampleCEOptFn", logits, labels, weight, pixel_weight)
+        _stat("upsample_ce_opt")
+        e0 = _tic()
+        sums, _, grad, _ = DL().upsample_ce(lg, lab, int(ignore_index), cw, float(label_smoothing), pw, False, True)
+        _toc("upsample_ce_opt", e0)
+        if reduction == "mean":
+            den = sums[1:2]
+            loss = sums[0:1] / den  # no valid (kept) pixel: 0 / 0 = NaN, like torch; no host sync
+            den = torch.where(den == 0, torch.ones_like(den), den)
+        else:
+            den = torch.ones_like(sums[1:2])
+            loss = sums[0:1]
+        ctx.save_for_backward(grad, den)
+        ctx.in_dtype = logits.dtype
+        return loss.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, den = ctx.saved_tensors
+        d = grad * (g.to(torch.float64) / den).to(torch.float32)
+        return d.to(ctx.in_dtype), None, None, None, None, None, None
+
+
+class UpsampleCEMapFn(torch.autograd.Function):
+    """reduction="none": the (B, H, W) loss map (times the pixel weight, when given) from the
+    forward-only launch; backward is one launch with the incoming gradient as the pixel weight, so
+    the map is differentiable and nothing K-wide at the label size ever exists."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, weight, label_smoothing, pixel_weight):
+        lg, lab, cw, pw = _ce_opt_args("UpsampleCEMapFn", logits, labels, weight, pixel_weight)
+        _stat("upsample_ce_opt")
+        e0 = _tic()
+        _, _, _, pl = DL().upsample_ce(lg, lab, int(ignore_index), cw, float(label_smoothing), None, True, False)
+        _toc("upsample_ce_opt", e0)
+        ctx.save_for_backward(lg, lab, cw, pw)
+        ctx.args = (int(ignore_index), float(label_smoothing), logits.dtype)
+        return pl if pw is None else pl * pw
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lab, cw, pw = ctx.saved_tensors
+        ignore_index, label_smoothing, in_dtype = ctx.args
+        q = g.to(torch.float32)
+        q = (q if pw is None else q * pw).contiguous()
+        _stat("upsample_ce_opt")
+        e0 = _tic()
+        _, _, grad, _ = DL().upsample_ce(lg, lab, ignore_index, cw, label_smoothing, q, False, True)
+        _toc("upsample_ce_opt", e0)
+        return grad.to(in_dtype), None, None, None, None, None
+
+
+def upsample_cross_entropy(logits, labels, ignore_index=255, weight=None, label_smoothing=0.0, pixel_weight=None,
+                           reduction="mean"):
+    """F.cross_entropy(F.interpolate(logits, labels.shape[-2:], mode="bilinear", align_corners=False),
+    labels, weight=weight, ignore_index=ignore_index, label_smoothing=label_smoothing,
+    reduction=reduction) on the low-res logits (B, K, h, w), K <= 256, without the resized tensor.
+    pixel_weight (B, H, W), any finite float: every pixel's loss is multiplied by it, and "mean"
+    divides by sum q w_t.  With no option set this is UpsampleCEFn, today's kernels."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"upsample_cross_entropy: reduction {reduction!r} (mean, sum or none)")
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError(f"upsample_cross_entropy: label_smoothing={label_smoothing} (0 <= label_smoothing < 1)")
+    if weight is None and float(label_smoothing) == 0.0 and pixel_weight is None and reduction == "mean":
+        return UpsampleCEFn.apply(logits, labels, ignore_index)
+    if reduction == "none":
+        return UpsampleCEMapFn.apply(logits, labels, ignore_index, weight, label_smoothing, pixel_weight)
+    return UpsampleCEOptFn.apply(logits, labels, ignore_index, weight, label_smoothing, pixel_weight, reduction)
 
 
 class UpsampleSILogFn(torch.autograd.Function):

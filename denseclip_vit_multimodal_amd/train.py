@@ -81,22 +81,59 @@ def loss_config(cfg):
             SILogLoss(lambd=float(sl.get("lambda", 0.5)), eps=float(sl.get("eps", 1e-6))))
 
 
-def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1):
+def seg_loss_config(cfg, num_classes):
+    """The segmentation loss of a trainer YAML, or None when it has none (the plain CE):
+    training.seg_loss: {class_weight: [num_classes floats], label_smoothing: x, ohem: {thresh:, min_kept:}},
+    every key optional.  Returns a losses.SegCrossEntropy for loss_fn's seg_loss."""
+    sl = ((cfg or {}).get("training", {}) or {}).get("seg_loss")
+    if sl is None:
+        return None
+    cw = sl.get("class_weight")
+    if cw is not None:
+        cw = [float(x) for x in cw]
+        if len(cw) != int(num_classes):
+            raise ValueError(f"training.seg_loss.class_weight: {len(cw)} weights for {num_classes} classes")
+        if any(not x >= 0.0 for x in cw):
+            raise ValueError("training.seg_loss.class_weight: a negative weight")
+    eps = float(sl.get("label_smoothing", 0.0))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"training.seg_loss.label_smoothing={eps} (0 <= label_smoothing < 1)")
+    ohem = sl.get("ohem")
+    if ohem is not None:
+        ohem = {"thresh": float(ohem.get("thresh", 0.7)), "min_kept": int(ohem.get("min_kept", 100000))}
+        if not 0.0 < ohem["thresh"] <= 1.0:
+            raise ValueError(f"training.seg_loss.ohem.thresh={ohem['thresh']} (0 < thresh <= 1)")
+        if ohem["min_kept"] < 0:
+            raise ValueError(f"training.seg_loss.ohem.min_kept={ohem['min_kept']} (>= 0)")
+    from .losses import SegCrossEntropy
+    return SegCrossEntropy(weight=cw, label_smoothing=eps, ignore_index=255, ohem=ohem)
+
+
+def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None):
     """seg_weight * CE(ignore 255) + silog_weight * SILog (train_denseclip.py:1265-1314; the
     weights and the SILog parameters come from the config, `loss_config`).  With a model in
     fused_head_loss mode the outputs are the heads' low-res maps and the resize + loss run
     as one fused kernel each (identical loss and gradients).  A batch whose labels are all
     ignored gives a NaN CE, as torch's CrossEntropyLoss does (the reference trainer then
-    skips the step, train_denseclip.py:1323)."""
+    skips the step, train_denseclip.py:1323).  seg_loss: a losses.SegCrossEntropy (`seg_loss_config`) in
+    the CE's place: class weights, label smoothing, OHEM; None is the plain CE."""
     silog = silog or SILogLoss()
     if out.get("main_output_lowres") is not None:
         from . import ops
-        loss = seg_weight * ops.UpsampleCEFn.apply(out["main_output_lowres"], seg, 255)
+        if seg_loss is None:
+            ce = ops.UpsampleCEFn.apply(out["main_output_lowres"], seg, 255)
+        else:
+            ce = seg_loss.fused(out["main_output_lowres"], seg)
+        loss = seg_weight * ce
         if out.get("depth_output_lowres") is not None:
             loss = loss + silog_weight * ops.UpsampleSILogFn.apply(out["depth_output_lowres"], depth, mask,
                                                                    silog.lambd, silog.eps)
         return loss
-    loss = seg_weight * F.cross_entropy(out["main_output"], seg, ignore_index=255)
+    if seg_loss is None:
+        ce = F.cross_entropy(out["main_output"], seg, ignore_index=255)
+    else:
+        ce = seg_loss(out["main_output"], seg)
+    loss = seg_weight * ce
     if out.get("depth_output") is not None:
         loss = loss + silog_weight * silog(out["depth_output"], depth, mask)
     return loss
@@ -619,13 +656,13 @@ def step_unless_nonfinite(opt, loss, check_grads=True):
         del opt.found_inf
 
 
-def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1):
+def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None):
     """One step: forward (DenseCLIP.forward train branch), loss, backward (DDP all-reduce
     overlapped with it), AdamW (skipped for a non-finite loss, step_unless_nonfinite).  Returns
     the loss tensor (no host sync)."""
     img, seg, depth, mask = batch
     out = model(img, gt_semantic_seg=seg, gt_depth=depth, return_loss=True)
-    loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight)
+    loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss)
     opt.zero_grad(set_to_none=True)
     loss.backward()
     # the gradients are checked too when the backward ran in fp16 (power-of-two scaled casts can
@@ -634,7 +671,8 @@ def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1):
     return loss.detach()
 
 
-def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silog_weight=0.1, clip_grad_norm=None):
+def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silog_weight=0.1, clip_grad_norm=None,
+                     seg_loss=None):
     """One optimizer step on the mean gradient of k = len(micro_batches) micro-batches
     (training.grad_accum_steps, train_denseclip.py:1154, 1314, 1356-1358): zero_grad, then forward /
     loss / backward per micro-batch — every one but the last inside the wrapper's no_sync(), so the
@@ -658,7 +696,7 @@ def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silo
         hold = i < k - 1 and hasattr(model, "no_sync")
         with (model.no_sync() if hold else contextlib.nullcontext()):
             out = model(img, gt_semantic_seg=seg, gt_depth=depth, return_loss=True)
-            loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight)
+            loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss)
             (loss if native else loss / k).backward()
         total = loss.detach() if total is None else total + loss.detach()
     mean = total / k
@@ -741,7 +779,8 @@ class CapturedTrainStep:
     tensor is read by every replay.  accum_steps=k: `batch` is a sequence of k micro-batches and the
     one graph holds k forward / backward passes and one update (train_step_accum)."""
 
-    def __init__(self, model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, warmup=3, accum_steps=1):
+    def __init__(self, model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, warmup=3, accum_steps=1,
+                 seg_loss=None):
         if isinstance(model, (torch.nn.parallel.DistributedDataParallel, GradAllReduce)):
             raise RuntimeError("CapturedTrainStep: one process only (the data-parallel all-reduce hooks are not captured)")
         if not all(g.get("fused") and g.get("capturable") for g in opt.param_groups):
@@ -764,6 +803,7 @@ class CapturedTrainStep:
             self.static = [None if t is None else t.detach().clone() for t in batch]
             step_fn, first = train_step, self.static
         args = (silog, seg_weight, silog_weight)
+        kw = {} if seg_loss is None else {"seg_loss": seg_loss}
         m = _unwrap(model)
         saved = getattr(m, "graph_text", None)
         if saved is not None:
@@ -774,11 +814,11 @@ class CapturedTrainStep:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 for _ in range(max(1, warmup)):  # caches, allocator pools, the weight-refresh descriptor
-                    step_fn(model, opt, first, *args)
+                    step_fn(model, opt, first, *args, **kw)
             torch.cuda.current_stream(dev).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.loss = step_fn(model, opt, first, *args)
+                self.loss = step_fn(model, opt, first, *args, **kw)
         finally:
             if saved is not None:
                 m.graph_text = saved

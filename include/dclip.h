@@ -451,6 +451,30 @@ int dclip_upsample_eval_seg_classes(int low_dt, const void* logits, int B, int K
                                     int lab_dt, int H, int W, int ignore_index, uint8_t* pred, int64_t* cm,
                                     double* loss_sum, unsigned long long* count, void* ws, void* stream);
 
+/* dclip_upsample_ce / dclip_upsample_ce_classes with F.cross_entropy's other arguments (csrc/celossopt.hip;
+ * additive to ABI 7), for every 1 <= K <= DCLIP_CLASSES_MAX: K = 19 keeps a pixel's values in registers, any
+ * other K walks the classes in chunks of 16.  For a valid pixel p (label t != ignore_index, tested first, and
+ * in [0, K)), u = up(logits)_p, P = softmax(u), w = class_weight (all 1 when null), Wsum = sum_k w_k,
+ * e = label_smoothing, q_p = pixel_weight[p] (1 when null; any finite float):
+ *     l_p      = (1 - e) w_t (-log P_t) + (e / K) sum_k w_k (-log P_k)
+ *     dl_p/du  = (1 - e) w_t (P - onehot_t) + (e / K) (P Wsum - w)
+ *     sums[0] += sum_p q_p l_p    sums[1] += sum_p q_p w_t    count += #valid (q plays no part)
+ *     pixel_loss[p] = l_p (without q_p); 0 at a pixel that is not valid (every element is written)
+ *     grad    += up^T(q_p dl_p/du)   (un-normalised and accumulated, as dclip_upsample_ce)
+ * sums[0] / sums[1] is F.cross_entropy(weight=w, label_smoothing=e, reduction="mean"); pixel_loss is
+ * reduction="none".  grad == null: forward only (no gradient pass, no tiles, no merge).  pixel_loss, and
+ * sums with count (both or neither), may be null; at least one output is required.  0 <= e < 1;
+ * B*H*W < 2^31.  With all-one weights, e = 0 and no pixel_weight, sums[0], count and grad are bitwise those
+ * of dclip_upsample_ce (K = 19) / dclip_upsample_ce_classes.
+ * ws: dclip_upsample_ce_opt_ws_floats(B, K, h, w) floats, 8-byte aligned, contents undefined on entry.  The
+ * same fixed summation orders, per-workgroup tiles and partials, merge and sums launches: no atomics, and
+ * sums, count, grad and pixel_loss repeat bit for bit.  Stream-ordered: one ws per call in flight.       */
+int64_t dclip_upsample_ce_opt_ws_floats(int B, int K, int h, int w);
+int dclip_upsample_ce_opt(int low_dt, const void* logits, int B, int K, int h, int w, const void* labels,
+                          int lab_dt, int H, int W, int ignore_index, const float* class_weight,
+                          float label_smoothing, const float* pixel_weight, float* pixel_loss, double* sums,
+                          unsigned* count, float* grad, float* ws, void* stream);
+
 /* Multi-scale + flip test-time ensembling fused into the evaluation above (the reference's aug_test,
  * denseclip.py:1005-1041 with test.py:91-96, without materialising one resized tensor per view).
  * A view is a low-res map (B, K, h, w) of low_dt (one dtype, B and K for all views) and a flip flag;
