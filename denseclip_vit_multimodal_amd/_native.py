@@ -111,6 +111,10 @@ _SIGS = {
     "dclip_upsample_ce_classes_ws_floats": [_i32, _i32, _i32, _i32],
     "dclip_upsample_ce_classes": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
                                   _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    # the score map's backward for every K <= 256 (csrc/scoregrad.hip)
+    "dclip_score_map_bwd_ws_floats": [_i32, _i32, _i32, _i32],
+    "dclip_score_map_bwd": [_c_void_p, _i32, _i64, _i64, _i64, _c_void_p, _c_void_p, _f32, _c_void_p, _i32, _i64,
+                            _i64, _i64, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     # the fused CE with class weights, label smoothing, pixel weights and the pixel loss (csrc/celossopt.hip)
     "dclip_upsample_ce_opt_ws_floats": [_i32, _i32, _i32, _i32],
     "dclip_upsample_ce_opt": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
@@ -233,6 +237,7 @@ def load(path=None):
         lib.dclip_upsample_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_upsample_ce_classes_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_ce_opt_ws_floats.restype = ctypes.c_int64
+        lib.dclip_score_map_bwd_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_eval_seg_classes_ws_bytes.restype = ctypes.c_int64
         lib.dclip_adamw_ws_bytes.restype = ctypes.c_int64
         lib.dclip_ensemble_eval_ws_bytes.restype = ctypes.c_int64

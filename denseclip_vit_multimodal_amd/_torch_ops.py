@@ -321,6 +321,11 @@ def _register_fakes():
     def _(v, bstride, row_off, ld, text, B, HW, eps):
         return _e(B, text.shape[1], HW, like=v, dtype=f32)
 
+    @reg("dclip_classes::score_map_bwd")
+    def _(v, bstride, row_off, ld, text, ds, scale, B, HW, eps, dv_dtype):
+        K, C = text.shape[1], text.shape[2]
+        return _e(B * HW, C, like=v, dtype=dv_dtype), _e(B, K, C, like=v, dtype=f32)
+
     @reg("dclip_classes::upsample_ce")
     def _(logits, labels, ignore_index):
         return (_e(1, like=logits, dtype=torch.float64), _e(1, like=logits, dtype=torch.int32),

@@ -1019,6 +1019,35 @@ Tensor score_map_classes(const Tensor& v, int64_t bstride, int64_t row_off, int6
     return out;
 }
 
+// the score map's backward (scoregrad.hip), any K <= 256: (dv, dt).  v is read in place through its strides; dv
+// is dense (B*HW, C) rows in the dtype asked for (f32 or v's), dt is (B, K, C) f32
+std::tuple<Tensor, Tensor> score_map_bwd(const Tensor& v, int64_t bstride, int64_t row_off, int64_t ld,
+                                         const Tensor& text, const Tensor& ds, double scale, int64_t B, int64_t HW,
+                                         double eps, at::ScalarType dv_dtype) {
+    check_gpu(text, "text");
+    check_gpu(ds, "ds");
+    TORCH_CHECK(text.scalar_type() == at::kFloat && text.dim() == 3 && text.size(0) == B,
+                "score_map_bwd: text (B, K, C) fp32");
+    const int64_t K = text.size(1), C = text.size(2);
+    TORCH_CHECK(K >= 1 && K <= CLASSES_MAX, "score_map_bwd: K=", K, " (1 <= K <= ", CLASSES_MAX, " classes)");
+    TORCH_CHECK(v.scalar_type() == at::kHalf || v.scalar_type() == at::kBFloat16,
+                "score_map_bwd: v must be float16 or bfloat16");
+    TORCH_CHECK(dv_dtype == at::kFloat || dv_dtype == v.scalar_type(), "score_map_bwd: dv_dtype float32 or v's dtype");
+    TORCH_CHECK(ds.scalar_type() == at::kFloat && ds.numel() == B * K * HW && ds.dim() >= 3 && ds.size(0) == B &&
+                    ds.size(1) == K, "score_map_bwd: ds (B, K, HW) fp32");
+    TORCH_CHECK(text.device() == v.device() && ds.device() == v.device(), "score_map_bwd: tensors on different devices");
+    check_rows(v, bstride, row_off, ld, B, HW, C);
+    c10::DeviceGuard g(v.device());
+    Tensor dv = at::empty({B * HW, C}, like(v, dv_dtype));
+    Tensor dt = at::empty({B, K, C}, like(v, at::kFloat));
+    Tensor ws = at::empty({dclip_score_map_bwd_ws_floats((int)B, (int)HW, (int)C, (int)K)}, like(v, at::kFloat));
+    DCLIP_CALL(dclip_score_map_bwd(v.data_ptr(), dt_code(v.scalar_type()), bstride, row_off, ld, ptr<float>(text),
+                                   ptr<float>(ds), (float)scale, dv.data_ptr(), dt_code(dv_dtype), HW * C, 0, C,
+                                   ptr<float>(dt), ptr<float>(ws), (int)B, (int)HW, (int)C, (int)K, (float)eps,
+                                   stream_of(v)));
+    return {dv, dt};
+}
+
 // dclip::upsample_ce for K <= 256: (loss sum f64[1], valid count i32[1], un-normalised low-res gradient f32)
 std::tuple<Tensor, Tensor, Tensor> upsample_ce_classes(const Tensor& logits, const Tensor& labels,
                                                        int64_t ignore_index) {
@@ -1608,10 +1637,13 @@ TORCH_LIBRARY(dclip_eval, m) {
 TORCH_LIBRARY(dclip_classes, m) {
     m.def("score_map(Tensor v, int bstride, int row_off, int ld, Tensor text, int B, int HW, float eps) -> Tensor");
     m.def("upsample_ce(Tensor logits, Tensor labels, int ignore_index) -> (Tensor, Tensor, Tensor)");
+    m.def("score_map_bwd(Tensor v, int bstride, int row_off, int ld, Tensor text, Tensor ds, float scale, int B, "
+          "int HW, float eps, ScalarType dv_dtype) -> (Tensor dv, Tensor dt)");
 }
 
 TORCH_LIBRARY_IMPL(dclip_classes, CUDA, m) {
     m.impl("score_map", &score_map_classes);
+    m.impl("score_map_bwd", &score_map_bwd);
     m.impl("upsample_ce", &upsample_ce_classes);
 }
 

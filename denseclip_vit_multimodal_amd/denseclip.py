@@ -9,6 +9,9 @@ Differences from the reference, all deliberate:
     behind the last map (read in place): the pooling as a strided row mean, vis_proj as an MFMA
     GEMM and the normalise-and-contract as a batched [K x C] . [C x pixels] MFMA product.  It is returned by `_process_features` and, exactly as
     in the reference, not used by the heads (denseclip.py:747);
+  * identity_head=dict(type='IdentityHead', loss_weight=0.4) is the published method the reference stubs
+    (denseclip.py:366-369, 870-871): in training the score map divided by tau is returned as auxiliary
+    segmentation logits and the branch runs under autograd (ops.ScoreMapFn, `_score_branch_train`);
   * the final logits/depth resize is the HIP bilinear kernel (fp32 output).
 """
 import logging
@@ -161,8 +164,24 @@ class DenseCLIP(nn.Module):
 
         self.auxiliary_head = None
         self.with_auxiliary_head = False
+        # ---- identity head (denseclip.py:366-369: a stub there): score map / tau as auxiliary logits
         self.identity_head = None
         self.with_identity_head = False
+        self.identity_loss_weight = None
+        if identity_head:
+            icfg = dict(identity_head)
+            if icfg.pop("type", "IdentityHead") != "IdentityHead":
+                raise ValueError(f"Unsupported identity_head type: {identity_head.get('type')}")
+            if icfg.get("align_corners", False):
+                raise NotImplementedError("identity_head.align_corners=True is not supported by the HIP resize kernels")
+            weight = icfg.get("loss_weight", 0.4)
+            ld = icfg.get("loss_decode")
+            if isinstance(ld, dict) and ld.get("loss_weight") is not None:
+                weight = ld["loss_weight"]  # the published configs' place for it
+            # in_channels / channels / num_classes / dropout_ratio: the head has no parameters
+            self.identity_head = IdentityHead()
+            self.with_identity_head = True
+            self.identity_loss_weight = float(weight)
 
         # ---- class-name tokens + learnable context (denseclip.py:373-408)
         self.texts = torch.cat([tokenize(c, context_length=self.fixed_text_context_length) for c in class_names])
@@ -251,6 +270,8 @@ class DenseCLIP(nn.Module):
         either way; the replay reads the parameters' values after the previous optimizer step,
         as an in-line replay would).  A no-op until the graph exists (the first call captures
         it in line) or when a text buffer was re-allocated since the capture."""
+        if self._score_trains() and self._text_needs_grad():
+            return  # the identity head differentiates the text path: _text_embeddings runs it in line, with autograd
         if self.graph_text == "side":  # serve.CapturedForward: the text path eager on the side stream, captured
             self._text_side_eager(device)
             return
@@ -300,6 +321,17 @@ class DenseCLIP(nn.Module):
         with torch.cuda.stream(side), torch.no_grad():
             out = self._text_forward(self._texts_dev)
         self._text_side_out = (out, side)
+
+    def _score_trains(self):
+        """The score branch is part of the training graph: an identity head, train mode, gradients on."""
+        return self.with_identity_head and self.training and torch.is_grad_enabled()
+
+    def _text_needs_grad(self):
+        if not torch.is_grad_enabled():
+            return False
+        if self.contexts is not None and self.contexts.requires_grad:
+            return True
+        return any(p.requires_grad for p in self.text_encoder.parameters())
 
     def _text_embeddings(self, B, device):
         """Class-name embeddings (denseclip.py:627-640).  The text path is batch-independent and,
@@ -364,7 +396,17 @@ class DenseCLIP(nn.Module):
         HW = h * w
         cdt = visual.dtype if visual.dtype in (torch.bfloat16, torch.float16) else \
             getattr(self.backbone, "compute_dtype", torch.float16)
-        # the score branch is forward-only, as in the reference: with score_concat_index >= 0 the
+        if self._score_trains():
+            if not visual.is_cuda:
+                raise RuntimeError("identity_head: the score branch trains on the HIP kernels only (a CPU map has no "
+                                   "fallback); call the model under torch.no_grad() or in eval mode on the CPU")
+            text, score = self._score_branch_train(visual, cdt)
+            feats = list(x)
+            if 0 <= self.score_concat_index < len(feats):
+                with torch.no_grad():  # still not fed to the neck, as in the reference (denseclip.py:747)
+                    feats[self.score_concat_index] = ops.score_concat(feats[self.score_concat_index], score.detach())
+            return text, feats, score, list(x)
+        # without an identity head the score branch is forward-only, as in the reference: with score_concat_index >= 0 the
         # reference concatenates the score map onto a CLONE of the maps and the forward passes
         # the unmodified maps to the neck (denseclip.py:586, 684-694, 747), so nothing trainable
         # is reached through it (its parameters are kept out of DDP: train.gradless_parameter_names)
@@ -406,6 +448,48 @@ class DenseCLIP(nn.Module):
                 feats[self.score_concat_index] = ops.score_concat(feats[self.score_concat_index], score)
         return text, feats, score, list(x)
 
+    def _score_branch_train(self, visual, cdt):
+        """The score branch under autograd (identity head, training): returns (text, score / tau), the
+        logits (B, K, h, w) f32.  vis_proj is ops.Conv1x1Fn over the last read-out map (its existing
+        GEMM, NT and weight-gradient kernels), the text path runs eagerly with gradients, gamma *
+        context_decoder stays torch autograd, and normalise + contract + 1 / tau is ops.ScoreMapFn.
+        The gradient reaches the backbone through `visual` (autograd adds it to the neck's)."""
+        if cdt == torch.float16:
+            raise NotImplementedError("identity_head with fp16 compute: the delayed head gradient scale (ops.HeadScale) "
+                                      "covers one gradient source; train the identity head in bf16")
+        B, Cv, h, w = visual.shape
+        if self.vis_proj is not None:
+            if Cv % 64 or self.vis_proj.out_channels % 16:
+                raise NotImplementedError(f"identity_head: vis_proj {Cv} -> {self.vis_proj.out_channels} has no HIP "
+                                          "GEMM (input width in 64s, output width in 16s)")
+            vmap = ops.Conv1x1Fn.apply(visual, self.vis_proj.weight, self.vis_proj.bias, cdt)
+        else:
+            vmap = visual if visual.dtype == cdt else visual.to(cdt)
+        Ct = vmap.shape[1]
+        text = self._text_embeddings(B, visual.device)
+        if self.context_decoder is not None:
+            vpix = vmap.permute(0, 2, 3, 1).reshape(B, h * w, Ct).float()
+            if self.context_feature == "attention":
+                g = visual.float().mean(dim=(2, 3))  # adaptive_avg_pool2d, with its gradient
+                if self.global_proj is not None:
+                    g = torch.nn.functional.linear(g, self.global_proj.weight, self.global_proj.bias)
+                ctx = torch.cat([g.unsqueeze(1), vpix], dim=1)
+            elif self.context_feature == "backbone":
+                ctx = vpix
+            else:
+                raise ValueError(f"Invalid context_feature type: {self.context_feature}")
+            with torch.autocast("cuda", enabled=False):
+                text = text.float() + self.gamma * self.context_decoder(text.float(), ctx)
+        if Ct != text.shape[2]:
+            raise ValueError(f"Visual dim after proj ({Ct}) != Text dim ({text.shape[2]}).")
+        logits = ops.ScoreMapFn.apply(vmap, text, 1e-12, 1.0 / self.tau)
+        return text, logits
+
+    def _identity_logits(self, score):
+        """What `_process_features` returned as the score, when it is the identity head's logits (score / tau
+        under autograd: `_score_branch_train` ran); None for the forward-only score map."""
+        return score if self._score_trains() else None
+
     def _heads(self, x_maps):
         if self.neck is not None:
             fused = self.neck(x_maps)
@@ -439,14 +523,15 @@ class DenseCLIP(nn.Module):
             if not isinstance(feats, (list, tuple)) or not feats:
                 raise RuntimeError("backbone returned no feature maps")
             feats = list(feats)
-            self._process_features(feats)  # score branch: computed and discarded (denseclip.py:747)
+            # score branch: computed and discarded (denseclip.py:747) unless an identity head trains on it
+            ident = self._identity_logits(self._process_features(feats)[2])
             with torch.autocast("cuda", dtype=cdt):
                 seg, depth = self._heads(feats)
         outs = [t for t in (seg, depth) if t is not None]
         res = list(ops.HeadsOutFn.apply(hs, *outs)) if outs else []
         seg = res.pop(0) if seg is not None else None
         depth = res.pop(0) if depth is not None else None
-        return seg, depth
+        return seg, depth, ident
 
     def forward(self, img, img_metas=None, gt_semantic_seg=None, return_loss=True, **kwargs):
         """denseclip.py:702-916.  Train: {'main_output','depth_output','aux_losses'};
@@ -455,10 +540,11 @@ class DenseCLIP(nn.Module):
             self._text_prelaunch(img.device)
         hcdt = self._hip_heads_dtype(img)
         if hcdt is not None:
-            seg, depth = self._forward_hip_heads(img, hcdt)
+            seg, depth, ident = self._forward_hip_heads(img, hcdt)
         else:
             feats = self.extract_feat(img)
-            self._process_features(feats)  # score branch: computed and discarded (denseclip.py:747)
+            # score branch: computed and discarded (denseclip.py:747) unless an identity head trains on it
+            ident = self._identity_logits(self._process_features(feats)[2])
             maps = feats
             param = next(self.neck.parameters()) if self.neck is not None else None
             if param is not None and maps[0].dtype != param.dtype and maps[0].is_cuda:
@@ -469,8 +555,11 @@ class DenseCLIP(nn.Module):
         if return_loss and self.training and self.fused_head_loss:
             # low-res head outputs for train.loss_fn's fused upsample + CE / SILog kernels
             # (same loss and gradients; the 1024x2048 logits are never materialised)
-            return {"main_output": None, "depth_output": None, "aux_losses": {},
-                    "main_output_lowres": seg, "depth_output_lowres": depth}
+            out = {"main_output": None, "depth_output": None, "aux_losses": {},
+                   "main_output_lowres": seg, "depth_output_lowres": depth}
+            if ident is not None:
+                out["identity_output_lowres"] = ident  # score / tau, (B, K, h, w) f32
+            return out
         if return_loss and self.training:
             gt = None
             for cand in (gt_semantic_seg, kwargs.get("gt_depth"), kwargs.get("depth_targets"),
@@ -482,7 +571,12 @@ class DenseCLIP(nn.Module):
                 seg = ops.upsample(seg, gt)
             if depth is not None and gt is not None and tuple(depth.shape[-2:]) != gt:
                 depth = ops.upsample(depth, gt)
-            return {"main_output": seg, "depth_output": depth, "aux_losses": {}}
+            aux = {}
+            if ident is not None:
+                if gt is not None and tuple(ident.shape[-2:]) != gt:
+                    ident = ops.upsample(ident, gt)
+                aux["identity_head"] = ident
+            return {"main_output": seg, "depth_output": depth, "aux_losses": aux}
         hw = tuple(img.shape[2:])
         if seg is not None and tuple(seg.shape[-2:]) != hw:
             seg = ops.upsample(seg, hw)
@@ -499,7 +593,7 @@ class DenseCLIP(nn.Module):
             self._text_prelaunch(img.device)
         hcdt = self._hip_heads_dtype(img)
         if hcdt is not None:
-            seg, depth = self._forward_hip_heads(img, hcdt)
+            seg, depth, _ = self._forward_hip_heads(img, hcdt)
         else:
             feats = self.extract_feat(img)
             self._process_features(feats)

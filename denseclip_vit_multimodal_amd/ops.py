@@ -529,6 +529,64 @@ def score_map(v, text, B, HW, row_off=0, bstride=None, eps=1e-12):
     return DC().score_map(v, bstride, row_off, C, text, B, HW, float(eps))
 
 
+def score_map_bwd(v, text, ds, B, HW, row_off=0, bstride=None, eps=1e-12, scale=1.0, dv_dtype=None):
+    """Gradients of `score_map` (csrc/scoregrad.hip, any K <= 256) for the upstream ds (B, K, HW) f32 times
+    `scale`: (dv, dt).  v is read in place like the forward's; dv (dv_dtype: f32 or v's, the default) is dense
+    (B*HW, C) rows; dt (B, K, C) f32."""
+    text = text.float().contiguous()
+    ds = ds.float().contiguous()
+    _check(text, ds)
+    C = v.shape[-1]
+    bstride = HW * C if bstride is None else bstride
+    if text.shape[1] > CLASSES_MAX:
+        raise ValueError(f"score_map_bwd: {text.shape[1]} classes (the fused kernels take at most {CLASSES_MAX})")
+    _stat("score_map_bwd")
+    return DC().score_map_bwd(v, bstride, row_off, C, text, ds, float(scale), B, HW, float(eps),
+                              dv_dtype if dv_dtype is not None else v.dtype)
+
+
+class ScoreMapFn(torch.autograd.Function):
+    """scale * score_map of a 16-bit (B, C, h, w) map and the text embeddings (B, K, C), differentiable with
+    respect to both (reference denseclip.py:672-675, followed by the identity head's 1 / tau).  Forward:
+    `score_map`'s dispatch on the map's pixel rows, read in place (a read-out map over its token buffer,
+    a channels-last map) — with scale 1 its result as it is.  Backward: one `score_map_bwd`; the map's
+    gradient comes back in the map's dtype as a channels-last map over dense (B*h*w, C) rows."""
+
+    @staticmethod
+    def forward(ctx, vmap, text, eps=1e-12, scale=1.0):
+        B, C, h, w = vmap.shape
+        HW = h * w
+        tok = token_rows(vmap)
+        if tok is not None and tok.dtype in (torch.bfloat16, torch.float16):
+            rows, bstride, off = tok, (HW + 1) * C, 1
+        else:
+            cdt = vmap.dtype if vmap.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
+            xr, bstride, _ = pixel_rows(vmap.detach(), cdt)
+            if bstride != HW * C:  # gaps between the images: one NHWC copy
+                xr, bstride = vmap.detach().to(cdt).permute(0, 2, 3, 1).contiguous(), HW * C
+            rows, off = xr.as_strided((B * HW, C), (C, 1)), 0
+        tx = text.detach().float().contiguous()
+        out = score_map(rows, tx, B, HW, row_off=off, bstride=bstride, eps=eps)
+        if scale != 1.0:
+            out = out * scale
+        ctx.save_for_backward(rows, tx)
+        ctx.meta = (B, C, h, w, off, bstride, float(eps), float(scale), vmap.dtype, text.dtype)
+        return out.view(B, -1, h, w)
+
+    @staticmethod
+    def backward(ctx, ds):
+        rows, tx = ctx.saved_tensors
+        B, C, h, w, off, bstride, eps, scale, v_dt, t_dt = ctx.meta
+        HW = h * w
+        dv, dt = score_map_bwd(rows, tx, ds.reshape(B, -1, HW), B, HW, row_off=off, bstride=bstride, eps=eps,
+                               scale=scale)
+        dmap = dv.as_strided((B, C, h, w), (HW * C, 1, w * C, C))
+        if dmap.dtype != v_dt:
+            dmap = dmap.to(v_dt)
+        return (dmap if ctx.needs_input_grad[0] else None, (dt.to(t_dt) if ctx.needs_input_grad[1] else None),
+                None, None)
+
+
 def score_concat(tgt, score):
     """torch.cat([tgt, upsample(score, tgt's size).to(tgt.dtype)], dim=1) — the score_concat_index
     branch (denseclip.py:684-694) — as one HIP pass when tgt is a 16-bit read-out map over its token
@@ -1613,7 +1671,13 @@ class Conv1x1Fn(torch.autograd.Function):
         d2 = d2.to(cdt).contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = gemm(d2, WEIGHTS.get(weight, cdt, transposed=True))
+            wt = WEIGHTS.get(weight, cdt, transposed=True)
+            dk = d2
+            if Cout % 64:  # the GEMM's K in 64s (DenseCLIP's vis_proj at a narrow text width): zero columns
+                Kp = _pad64(Cout)
+                dk = torch.nn.functional.pad(d2, (0, Kp - Cout))
+                wt = torch.nn.functional.pad(wt, (0, Kp - Cout))
+            dx = gemm(dk, wt)
             dx = dx.as_strided((B, Cin, H, W), (H * W * Cin, 1, W * Cin, Cin))
             if in_dt != cdt:
                 dx = dx.to(in_dt)

@@ -28,14 +28,33 @@ from .losses import SILogLoss
 # forward never passes on, denseclip.py:586, 684-694, 747).  They stay trainable — the
 # reference's AdamW param list holds them (train_denseclip.py:1040-1044, 1061), so optimizer
 # states interoperate — and are kept out of the DDP gradient reduction instead.
+#
+# With an identity head (DenseCLIP(identity_head=...)) the branch trains: score / tau is supervised as
+# segmentation logits, so the contexts and vis_proj get gradients, gamma and the ContextDecoder too when
+# one is configured, and global_proj when the decoder's context holds the pooled feature
+# (context_feature "attention").  Without a decoder the pooled feature feeds nothing: gamma and
+# global_proj stay dead.  backbone.proj is dead either way.
 _DEAD = ("backbone.proj", "contexts", "gamma")
 _DEAD_PREFIX = ("vis_proj.", "global_proj.", "context_decoder.")
 
 
+def _dead_names(m):
+    """(exact names, prefixes) of the parameters the model's configuration leaves without a gradient"""
+    if not getattr(m, "with_identity_head", False):
+        return _DEAD, _DEAD_PREFIX
+    if getattr(m, "context_decoder", None) is None:
+        return ("backbone.proj", "gamma"), ("global_proj.",)
+    if getattr(m, "context_feature", "attention") == "attention":
+        return ("backbone.proj",), ()
+    return ("backbone.proj",), ("global_proj.",)
+
+
 def gradless_parameter_names(model):
     """Trainable parameter names that get no gradient (DDP must not wait for them)."""
-    return [n for n, p in _unwrap(model).named_parameters()
-            if p.requires_grad and (n in _DEAD or n.startswith(_DEAD_PREFIX))]
+    m = _unwrap(model)
+    dead, prefix = _dead_names(m)
+    return [n for n, p in m.named_parameters()
+            if p.requires_grad and (n in dead or (bool(prefix) and n.startswith(prefix)))]
 
 
 def freeze_for_mode(model, mode):
@@ -81,6 +100,26 @@ def loss_config(cfg):
             SILogLoss(lambd=float(sl.get("lambda", 0.5)), eps=float(sl.get("eps", 1e-6))))
 
 
+def identity_loss_weight(cfg_or_model):
+    """The identity head's loss weight, or None without one.  A model: its head's (DenseCLIP(identity_head=
+    dict(loss_weight=...)), 0.4 in the published configs).  A trainer YAML: model.identity_head's
+    (loss_decode.loss_weight first, then loss_weight, then 0.4), overridden by training.loss_weights.identity."""
+    if isinstance(cfg_or_model, torch.nn.Module):
+        m = _unwrap(cfg_or_model)
+        return m.identity_loss_weight if getattr(m, "with_identity_head", False) else None
+    cfg = cfg_or_model or {}
+    head = (cfg.get("model", {}) or {}).get("identity_head")
+    if not head:
+        return None
+    w = ((cfg.get("training", {}) or {}).get("loss_weights", {}) or {}).get("identity")
+    if w is None:
+        ld = head.get("loss_decode")
+        w = ld.get("loss_weight") if isinstance(ld, dict) else None
+    if w is None:
+        w = head.get("loss_weight", 0.4)
+    return float(w)
+
+
 def seg_loss_config(cfg, num_classes):
     """The segmentation loss of a trainer YAML, or None when it has none (the plain CE):
     training.seg_loss: {class_weight: [num_classes floats], label_smoothing: x, ohem: {thresh:, min_kept:}},
@@ -109,15 +148,30 @@ def seg_loss_config(cfg, num_classes):
     return SegCrossEntropy(weight=cw, label_smoothing=eps, ignore_index=255, ohem=ohem)
 
 
-def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None):
+def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None, identity_weight=None):
     """seg_weight * CE(ignore 255) + silog_weight * SILog (train_denseclip.py:1265-1314; the
     weights and the SILog parameters come from the config, `loss_config`).  With a model in
     fused_head_loss mode the outputs are the heads' low-res maps and the resize + loss run
     as one fused kernel each (identical loss and gradients).  A batch whose labels are all
     ignored gives a NaN CE, as torch's CrossEntropyLoss does (the reference trainer then
     skips the step, train_denseclip.py:1323).  seg_loss: a losses.SegCrossEntropy (`seg_loss_config`) in
-    the CE's place: class weights, label smoothing, OHEM; None is the plain CE."""
+    the CE's place: class weights, label smoothing, OHEM; None is the plain CE.
+    identity_weight (`identity_loss_weight`): adds identity_weight * CE(identity logits, ignore 255), the plain
+    CE on the model's score map / tau (DenseCLIP(identity_head=...)): the fused resize + CE on
+    out["identity_output_lowres"], F.cross_entropy on out["aux_losses"]["identity_head"] otherwise.  Logits
+    without a weight raise: the head's parameters are counted as alive."""
     silog = silog or SILogLoss()
+    low = out.get("identity_output_lowres")
+    full = (out.get("aux_losses") or {}).get("identity_head")
+    if identity_weight is None and (low is not None or full is not None):
+        # the head's parameters count as alive (gradless_parameter_names): without the term they would get no
+        # gradient and GradAllReduce's buckets would never complete
+        raise ValueError("loss_fn: the model returned identity-head logits but no identity_weight was given "
+                         "(pass identity_weight=train.identity_loss_weight(model))")
+    if identity_weight is not None:
+        if low is None and full is None:
+            raise ValueError("loss_fn: identity_weight given but the model returned no identity logits "
+                             "(build it with identity_head=dict(type='IdentityHead', ...) and call it in training)")
     if out.get("main_output_lowres") is not None:
         from . import ops
         if seg_loss is None:
@@ -128,6 +182,8 @@ def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1,
         if out.get("depth_output_lowres") is not None:
             loss = loss + silog_weight * ops.UpsampleSILogFn.apply(out["depth_output_lowres"], depth, mask,
                                                                    silog.lambd, silog.eps)
+        if identity_weight is not None:
+            loss = loss + identity_weight * _identity_ce(low, full, seg)
         return loss
     if seg_loss is None:
         ce = F.cross_entropy(out["main_output"], seg, ignore_index=255)
@@ -136,7 +192,16 @@ def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1,
     loss = seg_weight * ce
     if out.get("depth_output") is not None:
         loss = loss + silog_weight * silog(out["depth_output"], depth, mask)
+    if identity_weight is not None:
+        loss = loss + identity_weight * _identity_ce(low, full, seg)
     return loss
+
+
+def _identity_ce(low, full, seg):
+    if low is not None:
+        from . import ops
+        return ops.upsample_cross_entropy(low, seg, ignore_index=255)
+    return F.cross_entropy(full, seg, ignore_index=255)
 
 
 # wrap_ddp's data-parallel implementation: "allreduce" (GradAllReduce: bucketed in-place
@@ -656,13 +721,14 @@ def step_unless_nonfinite(opt, loss, check_grads=True):
         del opt.found_inf
 
 
-def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None):
+def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None, identity_weight=None):
     """One step: forward (DenseCLIP.forward train branch), loss, backward (DDP all-reduce
     overlapped with it), AdamW (skipped for a non-finite loss, step_unless_nonfinite).  Returns
     the loss tensor (no host sync)."""
     img, seg, depth, mask = batch
     out = model(img, gt_semantic_seg=seg, gt_depth=depth, return_loss=True)
-    loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss)
+    loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss,
+                   identity_weight=identity_weight)
     opt.zero_grad(set_to_none=True)
     loss.backward()
     # the gradients are checked too when the backward ran in fp16 (power-of-two scaled casts can
@@ -672,7 +738,7 @@ def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, 
 
 
 def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silog_weight=0.1, clip_grad_norm=None,
-                     seg_loss=None):
+                     seg_loss=None, identity_weight=None):
     """One optimizer step on the mean gradient of k = len(micro_batches) micro-batches
     (training.grad_accum_steps, train_denseclip.py:1154, 1314, 1356-1358): zero_grad, then forward /
     loss / backward per micro-batch — every one but the last inside the wrapper's no_sync(), so the
@@ -696,7 +762,8 @@ def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silo
         hold = i < k - 1 and hasattr(model, "no_sync")
         with (model.no_sync() if hold else contextlib.nullcontext()):
             out = model(img, gt_semantic_seg=seg, gt_depth=depth, return_loss=True)
-            loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss)
+            loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss,
+                           identity_weight=identity_weight)
             (loss if native else loss / k).backward()
         total = loss.detach() if total is None else total + loss.detach()
     mean = total / k
@@ -776,11 +843,11 @@ class CapturedTrainStep:
     DESIGN.md §5), so the bench's fp16 line stays eager.
 
     FusedAdamW is accepted like a capturable torch AdamW; a learning rate held in a 1-element device
-    tensor is read by every replay.  accum_steps=k: `batch` is a sequence of k micro-batches and the
+    tensor is read by every replay.  identity_weight: the identity head's term (loss_fn).  accum_steps=k: `batch` is a sequence of k micro-batches and the
     one graph holds k forward / backward passes and one update (train_step_accum)."""
 
     def __init__(self, model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, warmup=3, accum_steps=1,
-                 seg_loss=None):
+                 seg_loss=None, identity_weight=None):
         if isinstance(model, (torch.nn.parallel.DistributedDataParallel, GradAllReduce)):
             raise RuntimeError("CapturedTrainStep: one process only (the data-parallel all-reduce hooks are not captured)")
         if not all(g.get("fused") and g.get("capturable") for g in opt.param_groups):
@@ -804,6 +871,8 @@ class CapturedTrainStep:
             step_fn, first = train_step, self.static
         args = (silog, seg_weight, silog_weight)
         kw = {} if seg_loss is None else {"seg_loss": seg_loss}
+        if identity_weight is not None:  # the text path then runs eagerly inside the capture, with autograd
+            kw["identity_weight"] = identity_weight
         m = _unwrap(model)
         saved = getattr(m, "graph_text", None)
         if saved is not None:

@@ -451,6 +451,28 @@ int dclip_upsample_eval_seg_classes(int low_dt, const void* logits, int B, int K
                                     int lab_dt, int H, int W, int ignore_index, uint8_t* pred, int64_t* cm,
                                     double* loss_sum, unsigned long long* count, void* ws, void* stream);
 
+/* Backward of the score map (csrc/scoregrad.hip; additive to ABI 7), one kernel family for every
+ * 1 <= K <= DCLIP_CLASSES_MAX.  With s[b,k,p] = <v_p / max(|v_p|, eps), t_k / max(|t_k|, eps)> and the upstream
+ * ds (B, K, HW) f32, every element multiplied by `scale` on load (a trainer passes 1 / tau):
+ *     rv = 1 / max(|v_p|, eps), vn = v rv          rt = 1 / max(|t_k|, eps), tn = t rt
+ *     dvn_p = sum_k ds[k,p] tn_k                   dtn_k = sum_p ds[k,p] vn_p
+ *     dv_p = rv (dvn_p - a_p vn_p <vn_p, dvn_p>)   dt_k = rt (dtn_k - a_k tn_k <tn_k, dtn_k>)
+ * a = 1 where the norm is >= eps and 0 where the clamp is active: autograd of F.normalize; an all-zero row
+ * gets dvn / eps (dtn / eps), finite in f32 for eps = 1e-12 and gradients of ordinary size.
+ * v: the forward's strided 16-bit pixel rows, read in place.  dv: image b's pixel p at dv + b*dv_bstride +
+ * (dv_row_off + p)*dv_ld, dv_dt F32 or v_dt; only the B*HW pixel rows are written (CLS rows of a token
+ * buffer and anything past HW keep their contents).  dt (B, K, C) f32 is overwritten, never accumulated into.
+ * No 16-bit rounding before the stores: the sums over classes and pixels are f32 FMAs, the norms, rv / rt and
+ * the two projections (differences of nearly equal terms) f64.  dt's sum over pixels goes through
+ * per-workgroup partials in ws (dclip_score_map_bwd_ws_floats(B, HW, C, K) floats, 16-byte aligned, contents
+ * undefined on entry) folded in a fixed order: no float atomics, the grid depends on the shapes alone, two
+ * runs are bitwise equal.  C % 16 == 0, C <= 2048, 16-byte aligned rows of v and dv, t and dt 16-byte
+ * aligned, B <= 65535.  Stream-ordered: one ws per call in flight.                                      */
+int64_t dclip_score_map_bwd_ws_floats(int B, int HW, int C, int K);
+int dclip_score_map_bwd(const void* v, int v_dt, int64_t bstride, int64_t row_off, int64_t ld, const float* t,
+                        const float* ds, float scale, void* dv, int dv_dt, int64_t dv_bstride, int64_t dv_row_off,
+                        int64_t dv_ld, float* dt, float* ws, int B, int HW, int C, int K, float eps, void* stream);
+
 /* dclip_upsample_ce / dclip_upsample_ce_classes with F.cross_entropy's other arguments (csrc/celossopt.hip;
  * additive to ABI 7), for every 1 <= K <= DCLIP_CLASSES_MAX: K = 19 keeps a pixel's values in registers, any
  * other K walks the classes in chunks of 16.  For a valid pixel p (label t != ignore_index, tested first, and
