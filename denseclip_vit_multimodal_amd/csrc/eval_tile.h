@@ -469,7 +469,8 @@ struct DepthSums {
             ++n_mask;
             const float dm = gtv - u[p];
             s_msq += (double)(dm * dm);
-            const float d = logf(fmaxf(u[p], eps)) - logf(fmaxf(gtv, eps));
+            // selects, not fmaxf (which returns eps for a NaN): a NaN depth or target reaches sum d, sum d^2
+            const float d = logf(u[p] < eps ? eps : u[p]) - logf(gtv < eps ? eps : gtv);
             s_d += (double)d;
             s_d2 += (double)d * (double)d;
             // compute_depth_errors: mask && min <= gt <= max, optionally clamped prediction

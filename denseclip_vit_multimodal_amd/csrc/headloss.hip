@@ -186,7 +186,9 @@ __global__ __launch_bounds__(NTH) void band_fold_kernel(const TL* __restrict__ l
                     } else {
                         if (!tm[u]) continue;
                         const float p = Y.l0 * ut[0] + Y.l1 * ub[0];
-                        const float d = logf(fmaxf(p, eps)) - logf(fmaxf(tg[u], eps));
+                        // a select, not fmaxf: fmaxf(NaN, eps) is eps, and a NaN depth or target must
+                        // reach the sums as it does through torch.clamp (the trainer then skips the step)
+                        const float d = logf(p < eps ? eps : p) - logf(tg[u] < eps ? eps : tg[u]);
                         if constexpr (MODE == 1) {
                             lsum += (double)d;
                             lsum2 += (double)d * (double)d;

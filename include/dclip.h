@@ -376,6 +376,10 @@ int dclip_conv3x3_wgrad(int ab_dt, const void* dY, int64_t ldy, int Nout, const 
  *                         eps)) - log(max(target, eps)) on the mask; pass 1 (sums complete):
  *                         grad (f32, B*h*w) += up^T((2d/T - 2 lambd S/T^2) / up(pred))
  *                         (zero where up(pred) < eps).  K == 19 for the CE kernel.
+ *                         A mask byte counts as valid when non-zero.  Masked-out targets may hold
+ *                         anything, NaN included: they are not used.  A NaN among the in-mask
+ *                         resized predictions or targets makes sums[0..1] NaN (max() here keeps a
+ *                         NaN, as torch.clamp does); T counts the pixel all the same.
  * ws (ABI 7): the caller's scratch of dclip_upsample_ws_floats(B, K, h, w) floats (K = 1 for
  * SILog), 8-byte aligned, contents undefined on entry: every workgroup writes its loss partials
  * and its low-res gradient tile there and two short launches add them in a fixed order, so the

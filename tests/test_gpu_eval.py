@@ -217,6 +217,31 @@ def test_depth_sums_and_resized_map(shape, low, mask_kind, clamp):
     check_depth_sums(sums, u64, R.depth_target(B, H, W), mask, bool(clamp))
 
 
+def test_depth_nan_prediction_reaches_the_silog_sums():
+    """One NaN in the low-res prediction under the mask: sums[10] (sum d) and sums[11] (sum d^2), d as in
+    dclip_upsample_silog, must not be finite -- torch.clamp in SILogLoss keeps the NaN, and a clamp
+    that returns eps for it would report a finite validation loss for a diverged depth head.  The
+    sliding-window and ensemble paths score through the same epilogue (eval_tile.h)."""
+    shape = R.SHAPES[0]
+    B, h, w, H, W = shape
+    low = R.depth_low(B, h, w, torch.float32).clone()
+    low.view(B, -1)[0, (h // 2) * w + w // 2] = float("nan")
+    mask = R.depth_mask(B, H, W)
+    u = R.resize(low, H, W)[:, 0]
+    assert int((torch.isnan(u) & (mask != 0)).sum()) > 0, "no masked-in pixel reads the NaN element"
+    lo, gt, mk = guarded_copy(low.to(DEV)), guarded_copy(R.depth_target(B, H, W).to(DEV)), guarded_copy(mask.to(DEV))
+    up, sums, ws = guarded((B, H, W), torch.float32), guarded(12, torch.float64), _ws(B, 1, h, w)
+    ws.fill(0xFF)
+    _call("dclip_upsample_eval_depth", LOW_DT[torch.float32], lo.ptr(), B, h, w, gt.ptr(), mk.ptr(), H, W, 1e-3, 80.0, 1,
+          1e-6, up.ptr(), sums.ptr(), ws.ptr(), _stream())
+    s = sums.t.cpu()
+    for g in (lo, gt, mk, up, sums, ws):
+        g.check()
+    print(f"NaN prediction under the mask: sum d {float(s[10])!r}, sum d^2 {float(s[11])!r}, n_mask {float(s[8])!r}")
+    assert float(s[8]) == float((mask != 0).sum())
+    assert not bool(torch.isfinite(s[10])) and not bool(torch.isfinite(s[11]))
+
+
 def _evaluator_on_fixture():
     from denseclip_vit_multimodal_amd.evaluate import Evaluator
     g = np.load(os.path.join(ROOT, "tests", "golden", "eval_metrics.npz"))
