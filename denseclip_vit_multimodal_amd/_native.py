@@ -144,6 +144,10 @@ _SIGS = {
     "dclip_cityscapes_prepare": [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p, _i32, _i32,
                                  _c_void_p, _c_void_p, _f32, _f32, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p,
                                  _c_void_p],
+    # ADE20K batch preparation on packed, variable-size planes (csrc/dataade.hip)
+    "dclip_ade20k_prepare_ws_bytes": [_c_void_p, _i32, _i32, _i32],
+    "dclip_ade20k_prepare": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p,
+                             _c_void_p, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _i64, _c_void_p],
     "dclip_attn_bwd_workspace": [_i32, _i32, _i32],
     "dclip_attn_bwd_fp8_workspace": [_i32, _i32, _i32],
     "dclip_attn_bwd_fp8": [_i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32,
@@ -158,6 +162,8 @@ _SIGS = {
 }
 EXPORTED = sorted(list(_SIGS) + ["dclip_last_error", "dclip_abi_version"])
 ENSEMBLE_MAX_VIEWS = 16
+ADE_GEOM_WORDS = 12  # DCLIP_ADE_GEOM_WORDS: int64 words per image of dclip_ade20k_prepare's geometry table
+U8 = 3  # DCLIP_U8
 CLASSES_MAX = 256  # DCLIP_CLASSES_MAX: the widest class count of the *_classes entry points (csrc/classes.hip)
 
 
@@ -243,6 +249,7 @@ def load(path=None):
         lib.dclip_ensemble_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_slide_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_slide_tta_eval_ws_bytes.restype = ctypes.c_int64
+        lib.dclip_ade20k_prepare_ws_bytes.restype = ctypes.c_int64
         # kernel-variant knobs for A/B runs: DCLIP_OPTIONS="id=value,..." (DCLIP_OPT_* ids of dclip.h)
         for kv in filter(None, os.environ.get("DCLIP_OPTIONS", "").split(",")):
             k, v = kv.split("=")

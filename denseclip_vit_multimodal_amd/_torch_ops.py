@@ -338,6 +338,12 @@ def _register_fakes():
                 _e(*logits.shape, like=logits, dtype=f32) if want_grad else None,
                 _e(*labels.shape, like=logits, dtype=f32) if want_pixel_loss else None)
 
+    # dclip_data::* — the ADE20K batch preparation on packed, variable-size planes (csrc/dataade.hip)
+    @reg("dclip_data::ade20k_prepare")
+    def _(img, lab, geom, geom_host, h, w, mean, std, ignore_label, out_dtype):
+        B = geom_host.shape[0]
+        return _e(B, 3, h, w, like=img, dtype=out_dtype), _e(B, h, w, like=img, dtype=torch.int64)
+
     # dclip_optim::* — the native AdamW step (csrc/optim.hip), a namespace of its own
     @reg("dclip_optim::adamw_prepare")
     def _(desc, desc_host, grads, tiles, hp, found_inf, state, with_norm):

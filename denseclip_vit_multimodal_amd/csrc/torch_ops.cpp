@@ -896,6 +896,52 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> cityscapes_prepare(const Tensor& img,
     return {out_img, seg, depth, mask};
 }
 
+// ----------------------------------------------------------------------------- ADE20K batch preparation
+// dclip_ade20k_prepare (dataade.hip): img / lab the packed uint8 planes of the batch, geom (B, 12) int64 on the
+// GPU and geom_host the same table on the CPU (validated there before any launch); ignore_label < 0: labels
+// unchanged; out_dtype Byte: the uint8 crop before the normalisation
+void ade20k_geom_check(const Tensor& geom_host, const char* op) {
+    TORCH_CHECK(geom_host.defined() && geom_host.is_cpu() && geom_host.is_contiguous() &&
+                    geom_host.scalar_type() == at::kLong && geom_host.dim() == 2 && geom_host.size(0) >= 1 &&
+                    geom_host.size(1) == DCLIP_ADE_GEOM_WORDS,
+                op, ": geom_host must be a contiguous (B >= 1, ", DCLIP_ADE_GEOM_WORDS, ") int64 CPU tensor");
+}
+
+int64_t ade20k_ws_bytes(const Tensor& geom_host, int64_t h, int64_t w) {
+    ade20k_geom_check(geom_host, "ade20k_ws_bytes");
+    TORCH_CHECK(h >= 1 && w >= 1 && h < (1 << 20) && w < (1 << 20), "ade20k_ws_bytes: crop ", h, "x", w);
+    const int64_t n = dclip_ade20k_prepare_ws_bytes((const int64_t*)geom_host.data_ptr(), (int)geom_host.size(0), (int)h,
+                                                    (int)w);
+    TORCH_CHECK(n >= 0, "dclip: ", dclip_last_error());
+    return n;
+}
+
+std::tuple<Tensor, Tensor> ade20k_prepare(const Tensor& img, const Tensor& lab, const Tensor& geom,
+                                          const Tensor& geom_host, int64_t h, int64_t w, at::ArrayRef<double> mean,
+                                          at::ArrayRef<double> stdv, int64_t ignore_label, at::ScalarType out_dtype) {
+    check_gpu(img, "img"); check_gpu(lab, "lab"); check_gpu(geom, "geom");
+    ade20k_geom_check(geom_host, "ade20k_prepare");
+    TORCH_CHECK(mean.size() == 3 && stdv.size() == 3, "ade20k_prepare: 3 means / stds");
+    TORCH_CHECK(img.scalar_type() == at::kByte && lab.scalar_type() == at::kByte && img.dim() == 1 && lab.dim() == 1,
+                "ade20k_prepare: img and lab must be flat uint8 buffers (the packed planes)");
+    TORCH_CHECK(geom.scalar_type() == at::kLong && geom.sizes() == geom_host.sizes(),
+                "ade20k_prepare: geom must be the GPU copy of geom_host");
+    TORCH_CHECK(ignore_label >= -1 && ignore_label <= 255, "ade20k_prepare: ignore_label in [0, 255], or -1 for none");
+    const int64_t B = geom_host.size(0);
+    const int64_t nws = ade20k_ws_bytes(geom_host, h, w);
+    c10::DeviceGuard g(img.device());
+    Tensor out_img = at::empty({B, 3, h, w}, like(img, out_dtype));
+    Tensor seg = at::empty({B, h, w}, like(img, at::kLong));
+    Tensor ws = at::empty({nws}, like(img, at::kByte));
+    const double m[3] = {mean[0], mean[1], mean[2]}, s[3] = {stdv[0], stdv[1], stdv[2]};
+    DCLIP_CALL(dclip_ade20k_prepare(ptr<uint8_t>(img), img.numel(), ptr<uint8_t>(lab), lab.numel(),
+                                    (const int64_t*)geom.data_ptr(), (const int64_t*)geom_host.data_ptr(), (int)B, (int)h,
+                                    (int)w, m, s, (int)ignore_label, out_img.data_ptr(),
+                                    out_dtype == at::kByte ? DCLIP_U8 : dt_code(out_dtype), ptr<int64_t>(seg),
+                                    ws.data_ptr(), nws, stream_of(img)));
+    return {out_img, seg};
+}
+
 // ----------------------------------------------------------------------------- fused head evaluation
 Tensor eval_ws(const Tensor& low, int64_t K) {
     return at::empty({dclip_upsample_eval_ws_bytes((int)low.size(0), (int)K, (int)low.size(2), (int)low.size(3))},
@@ -1688,3 +1734,12 @@ TORCH_LIBRARY_IMPL(dclip_optim, CUDA, m) {
     m.impl("adamw_prepare", &adamw_prepare);
     m.impl("adamw_update", &adamw_update);
 }
+
+// The ADE20K data path (dataade.hip), beside the pinned dclip:: set
+TORCH_LIBRARY(dclip_data, m) {
+    m.def("ade20k_prepare(Tensor img, Tensor lab, Tensor geom, Tensor geom_host, int h, int w, float[] mean, "
+          "float[] std, int ignore_label, ScalarType out_dtype) -> (Tensor img, Tensor seg)");
+    m.def("ade20k_ws_bytes(Tensor geom_host, int h, int w) -> int", &ade20k_ws_bytes);
+}
+
+TORCH_LIBRARY_IMPL(dclip_data, CUDA, m) { m.impl("ade20k_prepare", &ade20k_prepare); }

@@ -65,7 +65,8 @@ extern "C" {
 #define DCLIP_F32 0
 #define DCLIP_F16 1
 #define DCLIP_BF16 2
-#define DCLIP_U8 3    /* dclip_cityscapes_augment only: the uint8 HWC crop, before ColorJitter / Normalize */
+#define DCLIP_U8 3    /* dclip_cityscapes_augment (the uint8 HWC crop, before ColorJitter / Normalize) and
+                         dclip_ade20k_prepare (the uint8 CHW crop, before the normalisation) only */
 
 #define DCLIP_OK 0
 #define DCLIP_ERR_ARG (-1)
@@ -659,6 +660,37 @@ int dclip_cityscapes_augment(const uint8_t* img, const uint8_t* ids, const uint1
                              const int* params, int h, int w, const float* mean, const float* stdv, float bf,
                              float depth_max, void* out_img, int out_dt, int64_t* out_seg, float* out_depth,
                              uint8_t* out_mask, void* stream);
+
+/* ADE20K batch preparation (the reference's datasets/ade20k.py:57-185 per sample; csrc/dataade.hip).
+ * img: the decoded uint8 RGB (H, W, 3) images of B samples of any sizes, packed into one device buffer of
+ * img_bytes; lab: their uint8 (H, W) raw label planes (0 .. 150), packed likewise, lab_bytes.  geom: int64
+ * (B, DCLIP_ADE_GEOM_WORDS) on the device, geom_host the same table on the host; per image
+ *   0 img_off, 1 lab_off   byte offsets of its planes in img / lab
+ *   2 H0, 3 W0             the decoded size
+ *   4 H1, 5 W1             after the first resize (int(H s), int(W s) of the random scale s)
+ *   6 H2, 7 W2             after the second resize (ade20k.py:97-118; = H1, W1 without one)
+ *   8 y0, 9 x0             the crop's origin in the H2 x W2 image, window [y0, y0 + h) x [x0, x0 + w) inside it
+ *   10 flip                != 0: the crop mirrored horizontally (an extension; the reference never flips)
+ *   11                     reserved, 0
+ * Each resize is PIL's on 8-bit planes: BILINEAR for the image (separable, horizontal pass first, each pass
+ * rounded to uint8: out = clip(((1 << 21) + sum px k) >> 22) with k = int(0.5 + weight 2^22) from f64 triangle
+ * weights over [xmin, xmax) = int(center -+ support + 0.5), support = max(in / out, 1); a pass between equal
+ * sizes is skipped) and NEAREST for the labels (source index int(xo), xo = a / 2 then one `xo += a` per
+ * output coordinate, a = in / out).  Outputs: out_img (B, 3, h, w) out_dt = (float32(u8) / 255 - mean) / std
+ * evaluated in f64 (mean, stdv: 3 host doubles), or with out_dt DCLIP_U8 the uint8 crop itself in the same
+ * layout; out_seg int64 (B, h, w) = v - 1 for v > 0, ignore_label for 0 (ignore_label < 0: v unchanged).
+ * ws: dclip_ade20k_prepare_ws_bytes(geom_host, B, h, w) bytes (ws_bytes: what the caller holds), 16-byte
+ * aligned; -1 from the query: bad geometry (dclip_last_error).  Every geometry entry is validated on the host
+ * before any launch (sizes >= 1, window inside the image, planes inside the packed buffers, workspace size);
+ * the kernels repeat the checks on the device copy and skip an image whose row fails them.  No host
+ * synchronisation, no atomics: capturable, and two runs are bitwise equal.  Launch sizes follow geom_host: a
+ * captured call replays for device tables of the same geometry.                                          */
+#define DCLIP_ADE_GEOM_WORDS 12
+int64_t dclip_ade20k_prepare_ws_bytes(const int64_t* geom_host, int B, int h, int w);
+int dclip_ade20k_prepare(const uint8_t* img, int64_t img_bytes, const uint8_t* lab, int64_t lab_bytes,
+                         const int64_t* geom, const int64_t* geom_host, int B, int h, int w, const double* mean,
+                         const double* stdv, int ignore_label, void* out_img, int out_dt, int64_t* out_seg, void* ws,
+                         int64_t ws_bytes, void* stream);
 
 /* ColorJitter (albumentations, train_denseclip.py:152-155; `color_jitter: true`) in place on a
  * uint8 HWC batch img (B, h, w, 3) RGB: params (B, 8) f64 on the device = brightness, contrast,
