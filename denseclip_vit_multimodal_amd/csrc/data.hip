@@ -267,7 +267,10 @@ __global__ __launch_bounds__(256) void color_jitter_kernel(uint8_t* __restrict__
 #pragma clang fp contract(off)
     const int b = blockIdx.y;
     const double* p = prm + 8 * b;
-    const int op = (int)p[4 + pos];
+    const double opd = p[4 + pos];
+    // the host validates the order; an entry outside 0..3 (or NaN) must not index outside this row
+    if (!(opd >= 0.0 && opd < 4.0)) return;
+    const int op = (int)opd;
     const double f = p[op];
     if ((op == 3 && f == 0.0) || (op != 3 && f == 1.0)) return;  // the identity factor: untouched
     uint8_t* q = img + (int64_t)b * hw * 3;

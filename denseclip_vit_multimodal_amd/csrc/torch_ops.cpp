@@ -857,6 +857,20 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> cityscapes_prepare(const Tensor& img,
     check_gpu(img, "img"); check_gpu(ids, "ids"); check_gpu(disp, "disp"); check_gpu(crop, "crop");
     TORCH_CHECK(mean.size() == 3 && stdv.size() == 3, "cityscapes_prepare: 3 means / stds");
     TORCH_CHECK(img.dim() == 4 && img.size(3) == 3 && crop.scalar_type() == at::kInt, "cityscapes_prepare: shapes");
+    // the kernels read img / ids as bytes and disp as 16-bit words through plain pointers
+    TORCH_CHECK(img.scalar_type() == at::kByte && ids.scalar_type() == at::kByte,
+                "cityscapes_prepare: img and ids must be uint8 (got ", img.scalar_type(), " and ", ids.scalar_type(), ")");
+    TORCH_CHECK(disp.scalar_type() == at::kShort || disp.scalar_type() == at::kUInt16,
+                "cityscapes_prepare: disp must be a 2-byte integer tensor, the uint16 disparity bits (got ",
+                disp.scalar_type(), ")");
+    TORCH_CHECK(img.size(0) >= 1 && img.size(1) >= 1 && img.size(2) >= 1, "cityscapes_prepare: empty img");
+    TORCH_CHECK(ids.dim() == 3 && ids.sizes() == img.sizes().slice(0, 3) && disp.sizes() == ids.sizes(),
+                "cityscapes_prepare: ids and disp must be (B, H, W) = (", img.size(0), ", ", img.size(1), ", ",
+                img.size(2), ") like img (got ", ids.sizes(), " and ", disp.sizes(), ")");
+    TORCH_CHECK(ids.device() == img.device() && disp.device() == img.device() && crop.device() == img.device() &&
+                    (!jitter.has_value() || !jitter->defined() || jitter->device() == img.device()),
+                "cityscapes_prepare: every tensor must be on img's device");
+    TORCH_CHECK(h >= 1 && w >= 1 && h < (1 << 20) && w < (1 << 20), "cityscapes_prepare: crop ", h, "x", w);
     // crop (B, 3) = window + flip; crop (B, 7) = the RandomScale / PadIfNeeded parameters in front
     const bool aug = crop.dim() == 2 && crop.size(1) == 7;
     TORCH_CHECK(crop.dim() == 2 && (crop.size(1) == 3 || aug) && crop.size(0) == img.size(0),

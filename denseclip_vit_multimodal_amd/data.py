@@ -174,6 +174,17 @@ def prepare_batch(samples, crop_hw, crops, device, out_dtype=torch.bfloat16, mea
     for s in samples:
         if s[0].shape != (H, W, 3) or s[1].shape != (H, W) or s[2].shape != (H, W):
             raise ValueError("all samples of a batch must share one image size")
+    jt = None
+    if jitter is not None:
+        # the kernel indexes a row's factors by its order entries: refuse a bad table here
+        jt = torch.as_tensor(jitter, dtype=torch.float64).reshape(B, 8)
+        if not bool(torch.isfinite(jt).all()):
+            raise ValueError(f"ColorJitter parameters must be finite (got {jt.tolist()})")
+        if not bool((jt[:, 4:].sort(1).values == torch.arange(4, dtype=torch.float64)).all()):
+            raise ValueError(f"ColorJitter order must be a permutation of 0..3 per image (got {jt[:, 4:].tolist()})")
+        if bool((jt[:, :3] < 0).any()):
+            raise ValueError("ColorJitter brightness, contrast and saturation factors must not be negative "
+                             f"(got {jt[:, :3].tolist()})")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("prepare_batch runs on the GPU (no CPU fallback)")
@@ -188,9 +199,8 @@ def prepare_batch(samples, crop_hw, crops, device, out_dtype=torch.bfloat16, mea
     disp = up([s[2].view(np.int16) for s in samples])  # the uint16 bits through an int16 tensor
     cr = crops.to(dev)
     from .ops import D
-    jt = None
-    if jitter is not None:
-        jt = torch.as_tensor(jitter, dtype=torch.float64).reshape(B, 8).to(dev)
+    if jt is not None:
+        jt = jt.to(dev)
     out_img, seg, depth, mask = D().cityscapes_prepare(img, ids, disp, cr, h, w, [float(v) for v in mean],
                                                        [float(v) for v in std], float(bf), float(depth_max), out_dtype,
                                                        jt)

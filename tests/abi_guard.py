@@ -1,6 +1,7 @@
 """Guard-banded, poisoned buffers for tests that call the C ABI directly (test_gpu_abi_contract.py,
 test_gpu_gemm_contract.py, test_gpu_conv_contract.py, test_gpu_misc_contract.py,
-test_gpu_norm_contract.py, test_gpu_silog_contract.py).
+test_gpu_norm_contract.py, test_gpu_silog_contract.py, test_gpu_ade20k.py,
+test_gpu_cityscapes_contract.py).
 
 The op layer allocates every output and workspace with at::empty, and the caching allocator hands a
 second call the block the first one just freed — still holding the first call's (correct) result.
