@@ -120,6 +120,13 @@ _SIGS = {
     "dclip_upsample_ce_opt": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
                               _c_void_p, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                               _c_void_p],
+    # the depth loss as a weighted sum of SILog, L1 and BerHu (csrc/depthlossopt.hip)
+    "dclip_upsample_depth_loss_ws_floats": [_i32, _i32, _i32],
+    "dclip_upsample_depth_stats": [_i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _i32,
+                                   _c_void_p, _c_void_p, _c_void_p],
+    "dclip_upsample_depth_finish": [_i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
+                                    _i32, _f32, _f32, _f32, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                    _c_void_p],
     "dclip_upsample_eval_seg_classes_ws_bytes": [_i32, _i32, _i32, _i32],
     "dclip_upsample_eval_seg_classes": [_i32, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32, _i32,
                                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
@@ -243,6 +250,7 @@ def load(path=None):
         lib.dclip_upsample_eval_ws_bytes.restype = ctypes.c_int64
         lib.dclip_upsample_ce_classes_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_ce_opt_ws_floats.restype = ctypes.c_int64
+        lib.dclip_upsample_depth_loss_ws_floats.restype = ctypes.c_int64
         lib.dclip_score_map_bwd_ws_floats.restype = ctypes.c_int64
         lib.dclip_upsample_eval_seg_classes_ws_bytes.restype = ctypes.c_int64
         lib.dclip_adamw_ws_bytes.restype = ctypes.c_int64

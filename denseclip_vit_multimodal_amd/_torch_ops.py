@@ -338,6 +338,15 @@ def _register_fakes():
                 _e(*logits.shape, like=logits, dtype=f32) if want_grad else None,
                 _e(*labels.shape, like=logits, dtype=f32) if want_pixel_loss else None)
 
+    # the depth loss as a weighted sum of SILog, L1 and BerHu (csrc/depthlossopt.hip)
+    @reg("dclip_loss::upsample_depth_stats")
+    def _(pred, target, mask, eps, terms):
+        return _e(6, like=pred, dtype=torch.float64)
+
+    @reg("dclip_loss::upsample_depth_finish")
+    def _(pred, target, mask, stats, eps, lambd, terms, w_silog, w_l1, w_berhu, threshold, want_grad):
+        return (_e(1, like=pred, dtype=torch.float64), _e(*pred.shape, like=pred, dtype=f32) if want_grad else None)
+
     # dclip_data::* — the ADE20K batch preparation on packed, variable-size planes (csrc/dataade.hip)
     @reg("dclip_data::ade20k_prepare")
     def _(img, lab, geom, geom_host, h, w, mean, std, ignore_label, out_dtype):

@@ -1166,6 +1166,61 @@ std::tuple<Tensor, Tensor, c10::optional<Tensor>, c10::optional<Tensor>> upsampl
             want_pixel_loss ? c10::optional<Tensor>(pl) : c10::nullopt};
 }
 
+// dclip_loss::upsample_depth_*: the depth loss as a weighted sum of SILog, L1 and BerHu (depthlossopt.hip).
+// Every tensor the kernels index: the prediction (B, 1, h, w), the f32 target and the u8 mask (B, H, W)
+void check_depth_loss(const char* op, const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& mask) {
+    check_gpu(pred, "pred"); check_gpu(target, "target"); check_opt(mask, "mask");
+    TORCH_CHECK(pred.dim() == 4 && pred.size(1) == 1 && pred.numel() > 0, op, ": pred (B, 1, h, w), got ", pred.sizes());
+    TORCH_CHECK(target.scalar_type() == at::kFloat && target.dim() == 3 && target.size(0) == pred.size(0) &&
+                target.numel() > 0, op, ": target fp32 (B, H, W) with pred's B, got ", target.scalar_type(), " ",
+                target.sizes());
+    TORCH_CHECK(target.device() == pred.device(), op, ": target on another device");
+    if (mask.has_value() && mask->defined()) {
+        TORCH_CHECK(mask->scalar_type() == at::kByte && mask->sizes() == target.sizes(), op,
+                    ": mask uint8 with the target's shape, got ", mask->scalar_type(), " ", mask->sizes());
+        TORCH_CHECK(mask->device() == pred.device(), op, ": mask on another device");
+    }
+}
+
+// stats f64[6] = (sum d, sum d^2, T, sum e, max e, 0) of the terms' bit set (DCLIP_DEPTH_*), from zero
+Tensor upsample_depth_stats(const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& mask, double eps,
+                            int64_t terms) {
+    check_depth_loss("dclip_loss::upsample_depth_stats", pred, target, mask);
+    const int B = (int)pred.size(0), h = (int)pred.size(2), w = (int)pred.size(3);
+    c10::DeviceGuard g(pred.device());
+    Tensor stats = at::zeros({6}, like(pred, at::kDouble));
+    Tensor ws = at::empty({dclip_upsample_depth_loss_ws_floats(B, h, w)}, like(pred, at::kFloat));
+    DCLIP_CALL(dclip_upsample_depth_stats(dt_code(pred.scalar_type()), pred.data_ptr(), B, h, w, ptr<float>(target),
+                                          optr<uint8_t>(mask), (int)target.size(1), (int)target.size(2), (float)eps,
+                                          (int)terms, ptr<double>(stats), ptr<float>(ws), stream_of(pred)));
+    return stats;
+}
+
+// (sum b(e) f64[1], zero without a BerHu weight; d loss / d pred (low-res, f32) or none) from the complete stats
+std::tuple<Tensor, c10::optional<Tensor>> upsample_depth_finish(
+    const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& mask, const Tensor& stats, double eps,
+    double lambd, int64_t terms, double w_silog, double w_l1, double w_berhu, double threshold, bool want_grad) {
+    check_depth_loss("dclip_loss::upsample_depth_finish", pred, target, mask);
+    check_gpu(stats, "stats");
+    TORCH_CHECK(stats.scalar_type() == at::kDouble && stats.numel() == 6, "dclip_loss::upsample_depth_finish: stats "
+                "must be the 6 float64 of upsample_depth_stats, got ", stats.scalar_type(), " ", stats.sizes());
+    TORCH_CHECK(stats.device() == pred.device(), "dclip_loss::upsample_depth_finish: stats on another device");
+    TORCH_CHECK(want_grad || w_berhu > 0.0, "dclip_loss::upsample_depth_finish: nothing to compute (no gradient "
+                "asked for and no BerHu weight)");
+    const int B = (int)pred.size(0), h = (int)pred.size(2), w = (int)pred.size(3);
+    c10::DeviceGuard g(pred.device());
+    Tensor bsum = at::zeros({1}, like(pred, at::kDouble));
+    Tensor grad = want_grad ? at::zeros(pred.sizes(), like(pred, at::kFloat)) : Tensor();
+    Tensor ws = at::empty({dclip_upsample_depth_loss_ws_floats(B, h, w)}, like(pred, at::kFloat));
+    DCLIP_CALL(dclip_upsample_depth_finish(dt_code(pred.scalar_type()), pred.data_ptr(), B, h, w, ptr<float>(target),
+                                           optr<uint8_t>(mask), (int)target.size(1), (int)target.size(2), (float)eps,
+                                           (float)lambd, (int)terms, (float)w_silog, (float)w_l1, (float)w_berhu,
+                                           (float)threshold, ptr<double>(stats),
+                                           w_berhu > 0.0 ? ptr<double>(bsum) : nullptr, ptr<float>(grad),
+                                           ptr<float>(ws), stream_of(pred)));
+    return {bsum, want_grad ? c10::optional<Tensor>(grad) : c10::nullopt};
+}
+
 // the bytes of seg_update_classes' workspace for these sizes
 int64_t seg_classes_ws_bytes(int64_t B, int64_t K, int64_t h, int64_t w) {
     TORCH_CHECK(K >= 1 && K <= CLASSES_MAX, "seg_classes_ws_bytes: K=", K, " (1 <= K <= ", CLASSES_MAX, " classes)");
@@ -1712,9 +1767,18 @@ TORCH_LIBRARY(dclip_loss, m) {
     m.def("upsample_ce(Tensor logits, Tensor labels, int ignore_index, Tensor? class_weight, float label_smoothing, "
           "Tensor? pixel_weight, bool want_pixel_loss, bool want_grad) -> "
           "(Tensor sums, Tensor count, Tensor? grad, Tensor? pixel_loss)");
+    // the depth loss as a weighted sum of SILog, L1 and BerHu (depthlossopt.hip)
+    m.def("upsample_depth_stats(Tensor pred, Tensor target, Tensor? mask, float eps, int terms) -> Tensor");
+    m.def("upsample_depth_finish(Tensor pred, Tensor target, Tensor? mask, Tensor stats, float eps, float lambd, "
+          "int terms, float w_silog, float w_l1, float w_berhu, float threshold, bool want_grad) -> "
+          "(Tensor berhu_sum, Tensor? grad)");
 }
 
-TORCH_LIBRARY_IMPL(dclip_loss, CUDA, m) { m.impl("upsample_ce", &upsample_ce_opt); }
+TORCH_LIBRARY_IMPL(dclip_loss, CUDA, m) {
+    m.impl("upsample_ce", &upsample_ce_opt);
+    m.impl("upsample_depth_stats", &upsample_depth_stats);
+    m.impl("upsample_depth_finish", &upsample_depth_finish);
+}
 
 TORCH_LIBRARY_IMPL(dclip_eval, CUDA, m) {
     m.impl("upsample_argmax_classes", &upsample_argmax_classes);

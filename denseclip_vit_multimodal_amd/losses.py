@@ -1,5 +1,8 @@
-"""SILog depth loss (reference seg/denseclip/losses.py:7-78) and the segmentation cross-entropy with
-class weights, label smoothing and online hard example mining."""
+"""SILog depth loss (reference seg/denseclip/losses.py:7-78), the depth loss as a weighted sum of SILog, L1
+and BerHu, and the segmentation cross-entropy with class weights, label smoothing and online hard example
+mining."""
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -30,6 +33,86 @@ class SILogLoss(nn.Module):
         Tf = T.to(d.dtype).clamp(min=1)
         loss = (d ** 2).sum() / Tf - self.lambd * d.sum() ** 2 / Tf ** 2
         return torch.where(T > 0, loss, torch.zeros_like(loss))
+
+
+class DepthLoss(nn.Module):
+    """The depth loss as a weighted sum of the terms the reference's trainer chooses between
+    (configs/denseclip_multitask_cityscapes.yaml:67-70 LOSS_TYPE 'silog', 'berhu' or 'l1' with
+    BERHU_THRESHOLD 0.2; train_denseclip.py:1276-1312 "the sum of depth components"):
+        silog * SILog(lambd, eps) + l1 * L1 + berhu * BerHu(berhu_threshold)
+    on the mask M (every pixel without one), r = prediction - target, e = |r|, T = #M:
+        L1    = sum_M e / T
+        BerHu = sum_M b(e) / T,  b(e) = e if e <= c, else (e^2 + c^2) / (2 c),  c = berhu_threshold * max_M e
+    c is a constant (Laina et al.): it is detached, no gradient flows through the maximum.  It is the
+    maximum of THIS call's pixels, hence per rank and per micro-batch under data parallelism or gradient
+    accumulation.  An empty mask gives 0.  Weights finite and >= 0, at least one > 0.
+
+    forward(prediction, target, mask) is the materialised formulation on a prediction already at the
+    target's size: plain torch, differentiable, no host synchronisation; it runs anywhere.
+    fused(pred_lowres, target, mask) is the same loss from the low-res prediction through
+    ops.upsample_depth_loss: the resized prediction never exists."""
+
+    def __init__(self, silog=1.0, l1=0.0, berhu=0.0, lambd=0.5, eps=1e-6, berhu_threshold=0.2):
+        super().__init__()
+        ws = [float(silog), float(l1), float(berhu)]
+        if not all(math.isfinite(v) and v >= 0.0 for v in ws) or not any(v > 0.0 for v in ws):
+            raise ValueError(f"DepthLoss: weights silog={silog}, l1={l1}, berhu={berhu} "
+                             "(finite, >= 0, at least one > 0)")
+        if not 0.0 < float(berhu_threshold) <= 1.0:
+            raise ValueError(f"DepthLoss: berhu_threshold={berhu_threshold} (0 < berhu_threshold <= 1)")
+        self.silog, self.l1, self.berhu = ws
+        self.lambd, self.eps = lambd, eps
+        self.berhu_threshold = float(berhu_threshold)
+
+    def forward(self, prediction, target, mask=None):
+        if mask is not None and mask.shape != prediction.shape:
+            if mask.dim() == prediction.dim() - 1:
+                mask = mask.unsqueeze(1)
+            else:
+                raise ValueError(f"Mask shape {mask.shape} incompatible with prediction shape {prediction.shape}")
+        if mask is not None and mask.dtype != torch.bool:
+            mask = mask != 0  # a mask byte counts as valid when non-zero
+        loss = 0.0
+        if self.silog > 0:
+            loss = self.silog * SILogLoss(self.lambd, self.eps)(prediction, target, mask)
+        if self.l1 > 0 or self.berhu > 0:
+            r = prediction - target
+            if mask is not None:
+                r = torch.where(mask, r, torch.zeros_like(r))  # masked-out targets may hold anything
+                T = mask.sum()
+            else:
+                T = torch.tensor(float(r.numel()), device=r.device)
+            e = r.abs()
+            Tf = T.to(r.dtype).clamp(min=1)
+            if self.l1 > 0:
+                loss = loss + self.l1 * (e.sum() / Tf)
+            if self.berhu > 0:
+                # amax keeps a NaN, as the kernels' select does; the masked-out pixels hold e = 0 <= c
+                c = self.berhu_threshold * e.detach().amax()
+                safe = torch.where(c > 0, c, torch.ones_like(c))
+                b = torch.where(e <= c, e, (e * e + c * c) / (2 * safe))
+                loss = loss + self.berhu * (b.sum() / Tf)
+            loss = torch.where(T > 0, loss, torch.zeros_like(loss))
+        return loss
+
+    def fused(self, pred_lowres, target, mask=None):
+        from . import ops
+        return ops.upsample_depth_loss(pred_lowres, target, mask, silog=self.silog, l1=self.l1, berhu=self.berhu,
+                                       lambd=self.lambd, eps=self.eps, berhu_threshold=self.berhu_threshold)
+
+
+class L1DepthLoss(DepthLoss):
+    """mean |prediction - target| on the mask (the reference's LOSS_TYPE 'l1')"""
+
+    def __init__(self):
+        super().__init__(silog=0.0, l1=1.0)
+
+
+class BerHuLoss(DepthLoss):
+    """the reverse Huber loss on the mask (the reference's LOSS_TYPE 'berhu', BERHU_THRESHOLD 0.2)"""
+
+    def __init__(self, threshold=0.2):
+        super().__init__(silog=0.0, berhu=1.0, berhu_threshold=threshold)
 
 
 def ohem_keep(p_t, valid, thresh, batch_kept):

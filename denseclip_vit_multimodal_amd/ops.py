@@ -1960,3 +1960,77 @@ class UpsampleSILogFn(torch.autograd.Function):
         lambd, eps, in_dtype = ctx.args
         grad = D().upsample_silog_grad(pd, tg, mk, sums, float(eps), float(lambd))
         return (grad * g.to(torch.float32)).to(in_dtype), None, None, None, None
+
+
+DEPTH_SILOG, DEPTH_L1, DEPTH_BERHU = 1, 2, 4  # DCLIP_DEPTH_*: the bit set of dclip_upsample_depth_stats
+
+
+def _depth_weights(name, silog, l1, berhu, berhu_threshold):
+    ws = tuple(float(v) for v in (silog, l1, berhu))
+    if not all(math.isfinite(v) and v >= 0.0 for v in ws) or not any(v > 0.0 for v in ws):
+        raise ValueError(f"{name}: weights silog={silog}, l1={l1}, berhu={berhu} (finite, >= 0, at least one > 0)")
+    if not 0.0 < float(berhu_threshold) <= 1.0:
+        raise ValueError(f"{name}: berhu_threshold={berhu_threshold} (0 < berhu_threshold <= 1)")
+    return ws
+
+
+class UpsampleDepthLossFn(torch.autograd.Function):
+    """silog * SILog + l1 * L1 + berhu * BerHu (losses.DepthLoss) of F.interpolate(pred, (H, W), bilinear,
+    align_corners=False) against target on mask, without the resized prediction (csrc/depthlossopt.hip):
+    a stats pass, then a finish pass that takes BerHu's c = berhu_threshold * max |p - target| from the
+    stats (a constant of the call: no gradient through the maximum) and also produces the low-res
+    gradient, which backward scales, as UpsampleCEFn does.  Without a gradient to produce (no_grad) the
+    finish pass is the forward-only form, and is skipped when there is no BerHu sum to take.  The loss
+    is formed from the device-side sums: no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, silog, l1, berhu, lambd, eps, berhu_threshold):
+        w_s, w_1, w_b = _depth_weights("UpsampleDepthLossFn", silog, l1, berhu, berhu_threshold)
+        B, _, h, w = pred.shape
+        H, W = target.shape[-2:]
+        pd = pred.detach().contiguous()
+        tg = target.detach().reshape(B, H, W).float().contiguous()
+        mk = mask.reshape(B, H, W).to(torch.uint8).contiguous() if mask is not None else None
+        _check(pd, tg, mk)
+        terms = (DEPTH_SILOG if w_s > 0 else 0) | (DEPTH_L1 if w_1 > 0 else 0) | (DEPTH_BERHU if w_b > 0 else 0)
+        want_grad = bool(ctx.needs_input_grad[0])
+        _stat("upsample_depth_loss")
+        e0 = _tic()
+        stats = DL().upsample_depth_stats(pd, tg, mk, float(eps), terms)
+        bsum, grad = None, None
+        if want_grad or w_b > 0:
+            bsum, grad = DL().upsample_depth_finish(pd, tg, mk, stats, float(eps), float(lambd), terms, w_s, w_1, w_b,
+                                                    float(berhu_threshold), want_grad)
+        _toc("upsample_depth_loss", e0)
+        T = stats[2].clamp(min=1)
+        loss = torch.zeros_like(T)
+        if w_s > 0:
+            loss = loss + w_s * (stats[1] / T - lambd * stats[0] ** 2 / T ** 2)
+        if w_1 > 0:
+            loss = loss + w_1 * (stats[3] / T)
+        if w_b > 0:
+            loss = loss + w_b * (bsum[0] / T)
+        loss = torch.where(stats[2] > 0, loss, torch.zeros_like(loss))
+        if want_grad:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = pred.dtype
+        return loss.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return (grad * g.to(torch.float32)).to(ctx.in_dtype), None, None, None, None, None, None, None, None
+
+
+def upsample_depth_loss(pred, target, mask=None, silog=1.0, l1=0.0, berhu=0.0, lambd=0.5, eps=1e-6,
+                        berhu_threshold=0.2):
+    """losses.DepthLoss(silog, l1, berhu, lambd, eps, berhu_threshold)(F.interpolate(pred, target.shape[-2:],
+    mode="bilinear", align_corners=False), target, mask) on the low-res prediction (B, 1, h, w), without
+    the resized tensor.  BerHu's c is berhu_threshold times the largest in-mask |p - target| of THIS call
+    (per rank and per micro-batch), a constant for the gradient.  With only silog > 0 this is
+    UpsampleSILogFn, today's kernels, times the weight."""
+    w_s, w_1, w_b = _depth_weights("upsample_depth_loss", silog, l1, berhu, berhu_threshold)
+    if w_1 == 0.0 and w_b == 0.0:
+        loss = UpsampleSILogFn.apply(pred, target, mask, lambd, eps)
+        return loss if w_s == 1.0 else w_s * loss
+    return UpsampleDepthLossFn.apply(pred, target, mask, w_s, w_1, w_b, lambd, eps, berhu_threshold)

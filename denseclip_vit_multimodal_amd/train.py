@@ -15,6 +15,7 @@ Mode "R" is the reference regime (backbone + text frozen); mode "F" also trains 
 which exercises the HIP backward kernels (the north star's roofline applies there).
 """
 import contextlib
+import math
 
 import torch
 import torch.nn.functional as F
@@ -148,7 +149,47 @@ def seg_loss_config(cfg, num_classes):
     return SegCrossEntropy(weight=cw, label_smoothing=eps, ignore_index=255, ohem=ohem)
 
 
-def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None, identity_weight=None):
+def depth_loss_config(cfg):
+    """The depth loss of a trainer YAML, or None when it has none (the plain SILog): training.depth_loss is
+    either {type: silog | l1 | berhu} (the reference's LOSS_TYPE, configs/denseclip_multitask_cityscapes.yaml:
+    67-70) or {terms: {silog: 1.0, l1: 0.5, berhu: 0.5}} (a weighted sum; an absent term weighs 0), with an
+    optional berhu_threshold (0.2).  SILog's lambda / eps come from training.silog_loss, as loss_config reads
+    them.  Returns a losses.DepthLoss for loss_fn's depth_loss."""
+    tr = (cfg or {}).get("training", {}) or {}
+    dl = tr.get("depth_loss")
+    if dl is None:
+        return None
+    if not isinstance(dl, dict) or ("type" in dl) == ("terms" in dl):
+        raise ValueError("training.depth_loss: give either type (silog, l1 or berhu) or terms ({silog:, l1:, berhu:})")
+    unknown = set(dl) - {"type", "terms", "berhu_threshold"}
+    if unknown:
+        raise ValueError(f"training.depth_loss: unknown keys {sorted(unknown)} (type, terms, berhu_threshold)")
+    names = ("silog", "l1", "berhu")
+    if "type" in dl:
+        kind = str(dl["type"]).lower()
+        if kind not in names:
+            raise ValueError(f"training.depth_loss.type={dl['type']!r} (silog, l1 or berhu)")
+        w = {n: float(n == kind) for n in names}
+    else:
+        terms = dl["terms"]
+        if not isinstance(terms, dict) or not terms or set(terms) - set(names):
+            raise ValueError(f"training.depth_loss.terms={terms!r} (weights for silog, l1 and / or berhu)")
+        w = {n: float(terms.get(n, 0.0)) for n in names}
+        if any(not (math.isfinite(v) and v >= 0.0) for v in w.values()):
+            raise ValueError(f"training.depth_loss.terms={terms!r}: a weight is negative or not finite")
+        if not any(v > 0.0 for v in w.values()):
+            raise ValueError(f"training.depth_loss.terms={terms!r}: every weight is zero")
+    theta = float(dl.get("berhu_threshold", 0.2))
+    if not 0.0 < theta <= 1.0:
+        raise ValueError(f"training.depth_loss.berhu_threshold={theta} (0 < berhu_threshold <= 1)")
+    sl = tr.get("silog_loss", {}) or {}
+    from .losses import DepthLoss
+    return DepthLoss(silog=w["silog"], l1=w["l1"], berhu=w["berhu"], lambd=float(sl.get("lambda", 0.5)),
+                     eps=float(sl.get("eps", 1e-6)), berhu_threshold=theta)
+
+
+def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None, identity_weight=None,
+            depth_loss=None):
     """seg_weight * CE(ignore 255) + silog_weight * SILog (train_denseclip.py:1265-1314; the
     weights and the SILog parameters come from the config, `loss_config`).  With a model in
     fused_head_loss mode the outputs are the heads' low-res maps and the resize + loss run
@@ -159,7 +200,10 @@ def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1,
     identity_weight (`identity_loss_weight`): adds identity_weight * CE(identity logits, ignore 255), the plain
     CE on the model's score map / tau (DenseCLIP(identity_head=...)): the fused resize + CE on
     out["identity_output_lowres"], F.cross_entropy on out["aux_losses"]["identity_head"] otherwise.  Logits
-    without a weight raise: the head's parameters are counted as alive."""
+    without a weight raise: the head's parameters are counted as alive.
+    depth_loss: a losses.DepthLoss (`depth_loss_config`) in SILog's place: any weighted sum of SILog, L1 and
+    BerHu, the whole of it times silog_weight (the reference weights "the sum of depth components" by
+    loss_weights.silog, train_denseclip.py:1276-1312); `silog` is then unused.  None is the plain SILog."""
     silog = silog or SILogLoss()
     low = out.get("identity_output_lowres")
     full = (out.get("aux_losses") or {}).get("identity_head")
@@ -180,8 +224,11 @@ def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1,
             ce = seg_loss.fused(out["main_output_lowres"], seg)
         loss = seg_weight * ce
         if out.get("depth_output_lowres") is not None:
-            loss = loss + silog_weight * ops.UpsampleSILogFn.apply(out["depth_output_lowres"], depth, mask,
-                                                                   silog.lambd, silog.eps)
+            if depth_loss is None:
+                loss = loss + silog_weight * ops.UpsampleSILogFn.apply(out["depth_output_lowres"], depth, mask,
+                                                                       silog.lambd, silog.eps)
+            else:
+                loss = loss + silog_weight * depth_loss.fused(out["depth_output_lowres"], depth, mask)
         if identity_weight is not None:
             loss = loss + identity_weight * _identity_ce(low, full, seg)
         return loss
@@ -191,7 +238,8 @@ def loss_fn(out, seg, depth, mask, silog=None, seg_weight=1.0, silog_weight=0.1,
         ce = seg_loss(out["main_output"], seg)
     loss = seg_weight * ce
     if out.get("depth_output") is not None:
-        loss = loss + silog_weight * silog(out["depth_output"], depth, mask)
+        dl = silog if depth_loss is None else depth_loss
+        loss = loss + silog_weight * dl(out["depth_output"], depth, mask)
     if identity_weight is not None:
         loss = loss + identity_weight * _identity_ce(low, full, seg)
     return loss
@@ -721,14 +769,15 @@ def step_unless_nonfinite(opt, loss, check_grads=True):
         del opt.found_inf
 
 
-def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None, identity_weight=None):
+def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, seg_loss=None, identity_weight=None,
+               depth_loss=None):
     """One step: forward (DenseCLIP.forward train branch), loss, backward (DDP all-reduce
     overlapped with it), AdamW (skipped for a non-finite loss, step_unless_nonfinite).  Returns
     the loss tensor (no host sync)."""
     img, seg, depth, mask = batch
     out = model(img, gt_semantic_seg=seg, gt_depth=depth, return_loss=True)
     loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss,
-                   identity_weight=identity_weight)
+                   identity_weight=identity_weight, depth_loss=depth_loss)
     opt.zero_grad(set_to_none=True)
     loss.backward()
     # the gradients are checked too when the backward ran in fp16 (power-of-two scaled casts can
@@ -738,7 +787,7 @@ def train_step(model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, 
 
 
 def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silog_weight=0.1, clip_grad_norm=None,
-                     seg_loss=None, identity_weight=None):
+                     seg_loss=None, identity_weight=None, depth_loss=None):
     """One optimizer step on the mean gradient of k = len(micro_batches) micro-batches
     (training.grad_accum_steps, train_denseclip.py:1154, 1314, 1356-1358): zero_grad, then forward /
     loss / backward per micro-batch — every one but the last inside the wrapper's no_sync(), so the
@@ -763,7 +812,7 @@ def train_step_accum(model, opt, micro_batches, silog=None, seg_weight=1.0, silo
         with (model.no_sync() if hold else contextlib.nullcontext()):
             out = model(img, gt_semantic_seg=seg, gt_depth=depth, return_loss=True)
             loss = loss_fn(out, seg, depth, mask, silog, seg_weight, silog_weight, seg_loss=seg_loss,
-                           identity_weight=identity_weight)
+                           identity_weight=identity_weight, depth_loss=depth_loss)
             (loss if native else loss / k).backward()
         total = loss.detach() if total is None else total + loss.detach()
     mean = total / k
@@ -847,7 +896,7 @@ class CapturedTrainStep:
     one graph holds k forward / backward passes and one update (train_step_accum)."""
 
     def __init__(self, model, opt, batch, silog=None, seg_weight=1.0, silog_weight=0.1, warmup=3, accum_steps=1,
-                 seg_loss=None, identity_weight=None):
+                 seg_loss=None, identity_weight=None, depth_loss=None):
         if isinstance(model, (torch.nn.parallel.DistributedDataParallel, GradAllReduce)):
             raise RuntimeError("CapturedTrainStep: one process only (the data-parallel all-reduce hooks are not captured)")
         if not all(g.get("fused") and g.get("capturable") for g in opt.param_groups):
@@ -873,6 +922,8 @@ class CapturedTrainStep:
         kw = {} if seg_loss is None else {"seg_loss": seg_loss}
         if identity_weight is not None:  # the text path then runs eagerly inside the capture, with autograd
             kw["identity_weight"] = identity_weight
+        if depth_loss is not None:  # a losses.DepthLoss in SILog's place (loss_fn); BerHu's c is per micro-batch
+            kw["depth_loss"] = depth_loss
         m = _unwrap(model)
         saved = getattr(m, "graph_text", None)
         if saved is not None:

@@ -27,6 +27,9 @@
  *   dclip_conv3x3(_wgrad)      ViTFeatureFusionNeck 3x3 ConvBNReLU convs models.py:741-745
  *   dclip_upsample_ce/silog    logits/depth resize + CE / SILog losses denseclip.py:843-868,
  *                              train_denseclip.py:1265-1314, losses.py:21-78
+ *   dclip_upsample_depth_stats/finish  the depth loss as a weighted sum of SILog, L1 and BerHu on the resized
+ *                              depth, configs/denseclip_multitask_cityscapes.yaml:67-70,
+ *                              train_denseclip.py:1276-1312
  *   dclip_upsample_eval_seg/depth  validate()'s resize + argmax / confusion matrix / CE and depth
  *                              errors, train_denseclip.py:294-684, denseclip/utils.py:109-139,
  *                              utils/depth_metrics.py:12-88
@@ -393,6 +396,48 @@ int dclip_upsample_ce(int low_dt, const void* logits, int B, int K, int h, int w
 int dclip_upsample_silog(int pass, int low_dt, const void* pred, int B, int h, int w, const float* target,
                          const uint8_t* mask, int H, int W, float eps, float lambd, double* sums, float* grad,
                          float* ws, void* stream);
+
+/* The depth loss as any weighted sum of SILog, L1 and BerHu (the reference's LOSS_TYPE 'silog', 'berhu' or
+ * 'l1', configs/denseclip_multitask_cityscapes.yaml:67-70, and "the sum of depth components",
+ * train_denseclip.py:1276-1312) on the resized prediction, which is never materialised
+ * (csrc/depthlossopt.hip).  Additive to ABI 7; dclip_upsample_silog is untouched.
+ * pred (B, 1, h, w) low_dt; target f32 (B, H, W); mask u8 (B, H, W) or null; B*H*W < 2^31.  On the mask M
+ * (a non-zero byte; every pixel without a mask), p = up(pred) with dclip_upsample_silog's arithmetic,
+ * r = p - target, e = |r|, T = #M, T' = max(T, 1), d as in dclip_upsample_silog:
+ *     silog = sum d^2 / T' - lambd (sum d)^2 / T'^2
+ *     l1    = sum e / T'
+ *     berhu = sum b(e) / T',  b(e) = e if e <= c, else (e^2 + c^2) / (2 c),  c = threshold * max_M e
+ *             (c = 0 without a pixel).  c is a constant of the CALL (Laina et al.): no gradient flows through
+ *             the maximum, and the maximum is over this call's pixels only, hence per rank and per
+ *             micro-batch when the caller splits a batch.
+ *   dclip_upsample_depth_stats: terms is a bit set of DCLIP_DEPTH_*.  stats (f64[6]) = (sum d, sum d^2, T,
+ *       sum e, max e, unused): the sums are accumulated (+=), the maximum is max(start, .), T always, sum d
+ *       and sum d^2 with SILOG, sum e with L1 or BERHU, max e with BERHU; every other slot comes back as it
+ *       went in.  max e is an f32 value held exactly.
+ *   dclip_upsample_depth_finish: terms is the set `stats` was built for; a non-zero weight needs its bit.
+ *       Weights finite and >= 0, at least one > 0; 0 < threshold <= 1 with a BerHu weight.  stats is read
+ *       only.  berhu_sum (f64[1]) += sum b(e): required with w_berhu > 0, null otherwise.  grad (f32,
+ *       B*h*w, accumulated, or null for the forward-only form) += up^T of
+ *           w_silog * dclip_upsample_silog's pass-1 expression + w_l1 * sign(r) / T'
+ *           + w_berhu * (sign(r) / T' if e <= c else r / (c T'))        on M, sign(0) = 0,
+ *       so c = 0 never divides, and with T = 0 every element comes back bitwise as it went in.
+ * NaN follows dclip_upsample_silog's rule: one NaN among the in-mask resized predictions or targets makes
+ * sum e, max e (the maximum is a select that keeps a NaN) and sum b(e) NaN; T counts the pixel all the same;
+ * masked-out targets may hold anything.
+ * ws: the caller's scratch of dclip_upsample_depth_loss_ws_floats(B, h, w) floats, 8-byte aligned, contents
+ * undefined on entry.  Per-workgroup records and gradient tiles, folded in a fixed order by short launches:
+ * no float atomics, two runs are bitwise equal.  Stream-ordered: one ws per call in flight.          */
+#define DCLIP_DEPTH_SILOG 1
+#define DCLIP_DEPTH_L1 2
+#define DCLIP_DEPTH_BERHU 4
+int64_t dclip_upsample_depth_loss_ws_floats(int B, int h, int w);
+int dclip_upsample_depth_stats(int low_dt, const void* pred, int B, int h, int w, const float* target,
+                               const uint8_t* mask, int H, int W, float eps, int terms, double* stats, float* ws,
+                               void* stream);
+int dclip_upsample_depth_finish(int low_dt, const void* pred, int B, int h, int w, const float* target,
+                                const uint8_t* mask, int H, int W, float eps, float lambd, int terms, float w_silog,
+                                float w_l1, float w_berhu, float threshold, const double* stats, double* berhu_sum,
+                                float* grad, float* ws, void* stream);
 
 /* Fused bilinear upsample (align_corners=False) + evaluation of the heads, forward only: the
  * reference's validate() (train_denseclip.py:294-684: resize :461-467, CE :497, argmax :582, masked
